@@ -11,9 +11,15 @@ Multi-GPU (``torch.distributed.run``, one rank per GPU, RCCL): weak scaling -- e
 refines its own 128-hypothesis shard (N = 8 is BASELINE's "1k-hypothesis batch sharded
 across 8 GPUs") and the step ends with ONE all-gather of the refined poses.
 
-Prints one JSON line (rank 0) with the throughput, the roofline of the dominant kernel
-(fp32 MFMA implicit-GEMM conv, timed live with HIP events on its launch stream) and the
-CPU baseline (the oracle port of the reference algorithm on the host cores, bounded sample).
+A plain run sets up, warms up, times ``--steps`` steps and prints one JSON line (rank 0) with
+the throughput, ``ms_per_step`` and the roofline of the dominant kernel (fp32 MFMA
+implicit-GEMM conv, timed live with HIP events on its launch stream, in the timed steps).
+``--full`` adds everything that takes runs of its own: the CPU baseline (the oracle port of
+the reference algorithm on the host cores, bounded sample) and the same-run parity against it,
+the exact-fp32 pass, the other way into the job, the sustained-MFMA probe, the input-stage
+rates, the extra workloads (C3 / C5 / single-sample renders / EfficientNet-b3 / end-to-end)
+and the all-gather timing.  ``--dump-outputs DIR`` writes what the last timed step returned
+as ``DIR/<name>.npy`` (the inputs are seeded: two builds compare output for output).
 """
 
 from __future__ import annotations
@@ -183,7 +189,7 @@ def e2e_run(device, rank, world, lanes, coarse_precision, steps, warmup, run_det
                    final_labels=final.infos.label.tolist(), final_poses=final.poses.cpu().numpy(),
                    filtered_hyp=extra["coarse_filter"]["preds"].infos.hypothesis_id.tolist())
     return {"elapsed": elapsed, "steps": steps, "prof": prof, "conv_union_ms": conv_union_ms, "stage_ms_per_frame": stage_ms,
-            "timing_str": extra["timing_str"], "product": product,
+            "timing_str": extra["timing_str"], "product": product, "last_step": (final, extra),
             "job_inputs": dict(images=scene["images"][:, :3], K=scene["K"], labels=[store.labels[i] for i in scene["det_obj_ids"]], boxes=boxes,
                                wc=wc, wr=wr, packed=store.packed, points=store.mesh_db.points, store_labels=list(store.labels),
                                render_kw=dict(msaa=renderer.msaa, aniso=renderer.aniso))}
@@ -255,6 +261,12 @@ def bench_e2e(args, device, rank, world):
     r = e2e_run(device, rank, world, args.lanes or DEFAULT_LANES["E2E"], coarse_precision, args.steps, args.warmup, run_detector=args.run_detector)
     if r is None:
         return
+    if args.dump_outputs:
+        final, extra = r["last_step"]
+        arrays = collection_arrays("final", final)
+        for key in ("coarse", "coarse_filter", "refiner_all_hypotheses", "scoring", "refiner"):
+            arrays.update(collection_arrays(key, extra[key]["preds"]))
+        dump_outputs(args.dump_outputs, arrays)
     elapsed, prof, conv_union_ms = r["elapsed"], r["prof"], r["conv_union_ms"]
     # dominant backbone = the one with more conv time (the coarse net unless it runs in fp16); roofline of the issued
     # instruction, v_mfma_f32_32x32x16_f16: executed fp16-MFMA FLOPs (fp32-MFMA-time equivalents x 16) / conv time
@@ -296,6 +308,53 @@ def union_ms(intervals) -> float:
             union += a1 - max(a0, end)
             end = a1
     return union
+
+
+DUMP_BUDGET_BYTES = 64 << 20  # --dump-outputs: every file together
+
+
+def collection_arrays(prefix, coll) -> dict:
+    """``{name: array}`` of a ``(Pandas)TensorCollection`` -- or of a dict of them, such as the per-iteration results of
+    ``forward_refiner`` -- for :func:`dump_outputs`: its tensors and the numeric columns of its ``infos``."""
+    if isinstance(coll, dict):
+        return {k: v for key, c in coll.items() for k, v in collection_arrays(f"{prefix}_{key}", c).items()}
+    arrays = {f"{prefix}_{name}": t for name, t in coll.tensors.items()}
+    infos = getattr(coll, "infos", None)
+    if infos is not None:
+        arrays.update({f"{prefix}_{col}": infos[col].values for col in infos.columns if infos[col].dtype.kind in "biuf"})
+    return arrays
+
+
+def predictor_arrays(prefix, outputs) -> dict:
+    """``{name: tensor}`` of a predictor's ``forward`` result (``{"iteration=k": PosePredictorOutput}``) for :func:`dump_outputs`:
+    every tensor field of every iteration, the network outputs included."""
+    from happypose_amd.pose_predictor import PosePredictorOutput
+
+    arrays = {}
+    for it, out in outputs.items():
+        for field in PosePredictorOutput.__dataclass_fields__:
+            v = getattr(out, field)
+            if isinstance(v, torch.Tensor):
+                arrays[f"{prefix}_{it}_{field}"] = v
+            elif field == "network_outputs":
+                arrays.update({f"{prefix}_{it}_{field}_{k}": t for k, t in v.items() if isinstance(t, torch.Tensor)})
+    return arrays
+
+
+def dump_outputs(out_dir, arrays) -> None:
+    """``--dump-outputs``: every array of ``{name: tensor | ndarray}`` as ``out_dir/<name>.npy`` -- float64 where the source is
+    float64 or an integer / boolean column, float32 otherwise -- so that two builds can be compared output for output."""
+    import re
+
+    host = {}
+    for name, a in arrays.items():
+        a = np.asarray(a.detach().cpu().numpy() if isinstance(a, torch.Tensor) else a)
+        host[re.sub(r"[^A-Za-z0-9_.-]", "", name)] = a.astype(np.float64 if a.dtype == np.float64 or a.dtype.kind in "biu" else np.float32)
+    total = sum(a.nbytes for a in host.values())
+    assert len(host) == len(arrays) and total <= DUMP_BUDGET_BYTES, (len(host), len(arrays), total)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), a)
 
 
 def recorded_traffic(kind="conv"):
@@ -396,9 +455,10 @@ def quick_workload(device, workload, precision, n_lanes, steps=3, warmup=2, rend
     return res
 
 
-def estimator_entry(model, images, K, labels, TCO0, device):
+def estimator_entry(model, images, K, labels, TCO0, device, keep=None):
     """``step()`` through the entry point: ``CosyPoseEstimator.forward_refiner`` (bsz_objects = the whole table) on the C2 job;
-    returns the final poses ``[B, 4, 4]`` like the direct call's ``iteration=5`` output."""
+    returns the final poses ``[B, 4, 4]`` like the direct call's ``iteration=5`` output.  ``keep``: a dict that receives the
+    whole per-iteration result of the last call (``--dump-outputs``)."""
     import pandas as pd
 
     from happypose_amd.pose_estimator import CosyPoseEstimator, ObservationTensor
@@ -413,6 +473,8 @@ def estimator_entry(model, images, K, labels, TCO0, device):
 
     def step():
         preds, _ = est.forward_refiner(obs, data, n_iterations=N_ITERS)
+        if keep is not None:
+            keep["preds"] = preds
         return preds[f"iteration={N_ITERS}"].poses
 
     return step
@@ -599,14 +661,22 @@ def main():
     ap.add_argument("--run-detector", action="store_true", help="E2E: the frame also goes through the Mask-RCNN detector (random weights)")
     ap.add_argument("--entry", default="estimator", choices=["estimator", "predictor"],
                     help="C2 on one GPU: what a step calls -- CosyPoseEstimator.forward_refiner (the drop-in entry point, SURVEY.md 0.8: the "
-                         "default, pandas bookkeeping and the numerical guard's status query included) or the bare predictor's forward; the "
-                         "other one is timed beside it (key `estimator`)")
+                         "default, pandas bookkeeping and the numerical guard's status query included) or the bare predictor's forward; with "
+                         "--full the other one is timed beside it (key `estimator`)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check what takes runs of its own: the CPU baselines and the same-run "
+                         "parity against the CPU oracle, the exact-fp32 pass, the other way into the C2 job, the sustained-MFMA probe, "
+                         "the input-stage rates, the extra workloads and, with N > 1, the all-gather (the --no-* switches trim it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the timed path returned in its last timed step as DIR/<name>.npy (float32 / float64)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extra-workloads", action="store_true", help="skip the 3-step C3 / C5 runs appended to the C2 line")
     ap.add_argument("--no-cpu-1thread", action="store_true")
     ap.add_argument("--no-e2e-parity", action="store_true", help="skip the oracle estimator's run of the end-to-end job (about a minute of CPU)")
     ap.add_argument("--cpu-seconds", type=float, default=15.0)
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:  # no launcher: this process only spawns the ranks
         # (no device query here: it would initialise HIP in this parent, which only spawns; a rank without a GPU fails
@@ -657,27 +727,33 @@ def main():
     # C2 on one GPU: the step goes through the ENTRY POINT, CosyPoseEstimator.forward_refiner (CP/integrated/pose_estimator.py:249-356)
     # on the 128-row hypothesis table, bsz_objects = 128 -- pandas bookkeeping, the per-iteration result tables and the guard's status
     # query included (north_star: "run_inference_pipeline() stays the drop-in entry point"; SURVEY.md 0.8 names forward_refiner as
-    # what is timed).  --entry predictor times the bare model.forward instead; either way the other one is timed beside it.
+    # what is timed).  --entry predictor times the bare model.forward instead; either way --full times the other one beside it.
     via_estimator = args.workload == "C2" and world == 1 and args.entry == "estimator"
+    keep = {} if args.dump_outputs else None  # the last step's whole result, for --dump-outputs
     entry_step = None
-    if args.workload == "C2" and world == 1:
-        entry_step = estimator_entry(model, images, K, labels, TCO0, device)
+    if args.workload == "C2" and world == 1 and (via_estimator or args.full):
+        entry_step = estimator_entry(model, images, K, labels, TCO0, device, keep=keep if via_estimator else None)
 
     def step():
         if via_estimator:
             return entry_step()
         if args.workload == "C5":  # coarse scoring, one object (576 grid poses) per chunk and lane as in 8(e)
             ck = 576 * n_lanes
-            scores = [model.forward_coarse(images, K, labels[i:i + ck], TCO0[i:i + ck], im_ids=im_ids[i:i + ck])["logits"]
-                      for i in range(0, B, ck)]
-            poses, logits = TCO0, torch.cat(scores).reshape(-1)
+            outs = [model.forward_coarse(images, K, labels[i:i + ck], TCO0[i:i + ck], im_ids=im_ids[i:i + ck]) for i in range(0, B, ck)]
+            poses, logits = TCO0, torch.cat([o["logits"] for o in outs]).reshape(-1)
+            if keep is not None:
+                keep["coarse"] = outs
         elif sharded:
             return D.refine_sharded(model, images, K, labels, TCO0, N_ITERS, im_ids=im_ids)[0]
         else:
             out = model.forward(images, K, labels, TCO0, n_iterations=N_ITERS, im_ids=im_ids)
             poses, logits = out[f"iteration={N_ITERS}"].TCO_output, None
+            if keep is not None:
+                keep["forward"] = out
         if world > 1:
-            poses, _ = D.gather_poses(poses, logits, rank * B, world * B)
+            poses, gathered_logits = D.gather_poses(poses, logits, rank * B, world * B)
+            if keep is not None and logits is not None:
+                keep["gathered_logits"] = gathered_logits
         return poses
 
     def fence():
@@ -706,8 +782,19 @@ def main():
         poses = step()
     fence()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs and rank == 0:  # before anything else runs a step (graph replays and lanes reuse their buffers)
+        if "preds" in keep:
+            dump_outputs(args.dump_outputs, collection_arrays("refiner", keep["preds"]))
+        elif "forward" in keep and world == 1:
+            dump_outputs(args.dump_outputs, predictor_arrays("forward", keep["forward"]))
+        elif "coarse" in keep and world == 1:
+            dump_outputs(args.dump_outputs, {k: torch.cat([o[k] for o in keep["coarse"]]).reshape(-1) for k in ("logits", "scores")})
+        elif "gathered_logits" in keep:  # N > 1, coarse scoring: the logits of every rank, gathered
+            dump_outputs(args.dump_outputs, {"logits": keep["gathered_logits"]})
+        else:  # N > 1: the poses of every rank, gathered
+            dump_outputs(args.dump_outputs, {"poses": poses})
     instrumented_ms = None
-    if graphs:
+    if graphs and args.full:
         # events cannot be recorded inside a replayed graph: the per-launch timing of the roofline comes from the same K
         # steps run once more eagerly (the launches are identical; only the host's part differs), reported beside it
         model.backbone.set_profiling(True)  # also drops the captured graphs (ops.graph_epoch)
@@ -734,7 +821,7 @@ def main():
 
     # all-gather of the refined poses alone (N > 1): [N_local, 18] fp32 rows over RCCL
     all_gather_us = None
-    if world > 1:
+    if world > 1 and args.full:
         g_poses = poses[rank * B:(rank + 1) * B].contiguous() if poses.shape[0] == world * B else poses
         for _ in range(3):
             D.gather_poses(g_poses, None, rank * B, world * B)
@@ -747,7 +834,7 @@ def main():
 
     # the same job the OTHER way in (see `via_estimator` above), half as many steps
     estimator = None
-    if entry_step is not None:
+    if entry_step is not None and args.full:
         def direct_step():
             return model.forward(images, K, labels, TCO0, n_iterations=N_ITERS, im_ids=im_ids)[f"iteration={N_ITERS}"].TCO_output
         estimator = side_timing(direct_step if via_estimator else entry_step, device, max(3, args.steps // 2), poses, B)
@@ -772,7 +859,7 @@ def main():
     # the same job restricted to the exact-fp32 kernels (fp32 MFMA: Winograd / direct), a quarter of the steps, so the
     # line also carries the number of the build whose every multiply is an fp32 FMA (reported beside `value`)
     exact = None
-    if precision == "f32" and not args.no_exact_fp32:
+    if precision == "f32" and args.full and not args.no_exact_fp32:
         model.backbone.set_conv_algo("winograd")  # this network only
         k_exact = max(2, args.steps // 4)
         step()
@@ -853,28 +940,32 @@ def main():
             line["roofline"]["timed_in"] = ("a second, eager pass of the same %d steps (%.2f ms/step): HIP events cannot be recorded inside "
                                             "a replayed graph; `value` is the graph-replayed pass" % (args.steps, instrumented_ms))
             line["eager_ms_per_step"] = instrumented_ms
+        elif graphs:  # no conv stretches were timed: HIP events cannot be recorded inside a replayed graph
+            line["roofline"] = {"bound": "mfma", "timed_in": "not measured: --full times the conv launches in a second, eager pass of the steps"}
         # what the matrix pipe SUSTAINS on this box (hp_probe_mfma_rate, measured now): gfx950 clocks to its power
         # budget, so back-to-back fp16 MFMAs on random operands settle at ~1.6 GHz and ~2/3 of the nominal dense peak --
         # the ceiling any dense fp16-MFMA kernel on real data is bound by
-        try:
-            sus_tf, sus_mhz = _ops.probe_mfma_rate(device, random_data=True)
-            nom_tf, nom_mhz = _ops.probe_mfma_rate(device, random_data=False)
-            line["roofline"]["sustained"] = {
-                "random_operands": {"tflops": sus_tf, "shader_mhz": sus_mhz}, "zero_operands": {"tflops": nom_tf, "shader_mhz": nom_mhz},
-                "frac_of_sustained": executed_f16 / sus_tf if sus_tf > 0 else None,
-                "note": "hp_probe_mfma_rate in this run: v_mfma_f32_32x32x16_f16 back to back on every SIMD, operands in registers; "
-                        "the power budget, not the issue rate, sets the clock (zeros reach the nominal peak)"}
-        except Exception as e:  # diagnostics only
-            line["roofline"]["sustained"] = {"error": str(e)}
+        if args.full:
+            try:
+                sus_tf, sus_mhz = _ops.probe_mfma_rate(device, random_data=True)
+                nom_tf, nom_mhz = _ops.probe_mfma_rate(device, random_data=False)
+                line["roofline"]["sustained"] = {
+                    "random_operands": {"tflops": sus_tf, "shader_mhz": sus_mhz}, "zero_operands": {"tflops": nom_tf, "shader_mhz": nom_mhz},
+                    "frac_of_sustained": executed_f16 / sus_tf if sus_tf > 0 else None,
+                    "note": "hp_probe_mfma_rate in this run: v_mfma_f32_32x32x16_f16 back to back on every SIMD, operands in registers; "
+                            "the power budget, not the issue rate, sets the clock (zeros reach the nominal peak)"}
+            except Exception as e:  # diagnostics only
+                line["roofline"]["sustained"] = {"error": str(e)}
         if all_gather_us is not None:
             line["all_gather_us"] = all_gather_us
         if ranks_block is not None:
             line["ranks"] = ranks_block
+        if args.workload == "C2" and world == 1:  # what a timed step calls
+            line["entry"] = ("CosyPoseEstimator.forward_refiner(observation, data_TCO_input[128], n_iterations=5), bsz_objects=128" if via_estimator
+                             else "CosyPosePosePredictor.forward (two lanes)")
         if estimator is not None:
             # `value` is timed through `entry`; `estimator` holds both ways in and the entry point's cost over the bare predictor
             est_ms, pred_ms = (line["ms_per_step"], estimator["ms_per_step"]) if via_estimator else (estimator["ms_per_step"], line["ms_per_step"])
-            line["entry"] = ("CosyPoseEstimator.forward_refiner(observation, data_TCO_input[128], n_iterations=5), bsz_objects=128" if via_estimator
-                             else "CosyPosePosePredictor.forward (two lanes)")
             line["estimator_ms_per_step"] = est_ms
             line["estimator"] = {"entry_ms_per_step": est_ms, "predictor_ms_per_step": pred_ms, "entry_value": B / (est_ms * 1e-3),
                                  "predictor_value": B / (pred_ms * 1e-3), "unit": "refined poses/s", "overhead_vs_predictor": est_ms / pred_ms - 1.0,
@@ -902,9 +993,9 @@ def main():
                 "note": "same job with hp_net_set_conv_algo(WINOGRAD): every multiply an fp32 FMA on the fp32 matrix path"}
         # launches of kernels that use scratch (spilled tile variants; they would also keep hipGraph replay off): 0 expected
         line["scratch_launches"] = int(_ops.scratch_launches())
-        if args.workload == "C2":
+        if args.workload == "C2" and args.full:
             line["stages"] = stage_rates(store, scene, images[:1], K[:1], TCO0[:B], im_ids[:B], device)
-        if args.workload == "C2" and world == 1 and not args.no_extra_workloads:
+        if args.workload == "C2" and world == 1 and args.full and not args.no_extra_workloads:
             # the other single-GPU configurations of BASELINE.json, 3 steps each, so that the driver's record carries them
             extras = [("c3", "C3", "f32", None), ("c5", "C5", "f16", None)]
             if args.render_state == "reference" and args.arch == "resnet34" and precision == "f32":
@@ -950,7 +1041,7 @@ def main():
                 except Exception as e:
                     line.setdefault("e2e", {"error": f"{type(e).__name__}: {e}"})
                     line.setdefault("e2e_f16_coarse", {"error": f"{type(e).__name__}: {e}"})
-        if not args.no_cpu_baseline and args.workload == "C2" and world == 1:  # the CPU baseline is a 1-GPU-run item
+        if args.full and not args.no_cpu_baseline and args.workload == "C2" and world == 1:  # the CPU baseline is a 1-GPU-run item
             rk = dict(msaa=renderer.msaa, aniso=renderer.aniso)  # the same render state on both sides
             base, cpu_poses = cpu_baseline(store, scene, weights, args.arch, args.cpu_seconds, render_kw=rk)
             line["cpu_baseline"] = base

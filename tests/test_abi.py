@@ -114,5 +114,12 @@ def test_first_launch_and_debug_table_are_race_free(tmp_path):
     env = {**os.environ, "HP_PP_GRID": "64", "HP_NET_SYNC": "yes", "TSAN_OPTIONS": "halt_on_error=1 exitcode=66"}
     for k in ("HP_PROFILE_LAYERS", "HP_CONV_NO_PP"):
         env.pop(k, None)
-    r = subprocess.run([str(exe)], env=env, capture_output=True, text=True, timeout=300)
+    # GCC's TSan runtime expects the address layout of the default ASLR entropy: on kernels with more mmap randomisation bits it
+    # aborts before main ("unexpected memory mapping").  The binary runs with address randomisation off for this one process
+    # (personality ADDR_NO_RANDOMIZE) wherever setarch may set it.
+    run = [str(exe)]
+    arch = os.uname().machine
+    if shutil.which("setarch") and subprocess.run(["setarch", arch, "-R", "true"], capture_output=True).returncode == 0:
+        run = ["setarch", arch, "-R", str(exe)]
+    r = subprocess.run(run, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0 and "ok" in r.stdout and "ThreadSanitizer" not in r.stderr, (r.returncode, r.stdout[-500:], r.stderr[-2000:])

@@ -474,3 +474,40 @@ def test_bench_e2e_parity_is_relative_to_the_oracle_spread():
     bad = dict(good, coarse_logit=cl + np.where(inst == 1, 0.2 * cl[inst == 1].std(), 0.0))
     q = bench.e2e_parity(bad, ref, "f16")
     assert not q["ok"] and q["coarse_logit_max_diff_over_spread"] > bench.COARSE_LOGIT_REL["f16"] and q["coarse_logit_max_abs_diff"] < 2e-2
+
+
+def test_bench_dump_outputs_writes_what_a_caller_receives(tmp_path, monkeypatch):
+    """``bench.py --dump-outputs``: the tensors and numeric ``infos`` columns of the estimator's per-iteration tables and every
+    tensor field of a predictor's result, one ``<name>.npy`` each -- float64 where the source is float64 or integer, float32
+    otherwise -- and nothing beyond the 64 MB budget."""
+    import importlib
+    import sys
+
+    from happypose_amd.pose_predictor import PosePredictorOutput
+    from happypose_amd.tensor_collection import PandasTensorCollection
+
+    root = str(Path(__file__).resolve().parent.parent)
+    if root not in sys.path:
+        sys.path.insert(0, root)
+    bench = importlib.import_module("bench")
+    poses = torch.arange(32, dtype=torch.float32).reshape(2, 4, 4)
+    infos = pd.DataFrame({"label": ["a", "b"], "instance_id": [0, 7], "coarse_logit": np.array([0.5, 0.25])})
+    preds = {f"iteration={k}": PandasTensorCollection(infos, poses=poses + k) for k in (1, 2)}
+    z = torch.zeros
+    out = PosePredictorOutput(TCO_output=poses, TCO_input=poses - 1, renders=None, images_crop=None, TCV_O_input=poses, KV_crop=z(2, 1, 3, 3),
+                              tCR=z(2, 3), labels=["a", "b"], K=z(2, 3, 3), K_crop=z(2, 3, 3), network_outputs={"pose": z(2, 9, dtype=torch.float16)},
+                              boxes_rend=z(2, 4), boxes_crop=z(2, 4))
+    arrays = dict(bench.collection_arrays("refiner", preds), **bench.predictor_arrays("forward", {"iteration=1": out}))
+    bench.dump_outputs(str(tmp_path / "out"), arrays)
+    got = {p.stem: np.load(p) for p in (tmp_path / "out").iterdir()}
+    assert {"refiner_iteration1_poses", "refiner_iteration2_poses", "refiner_iteration2_instance_id", "refiner_iteration2_coarse_logit",
+            "forward_iteration1_TCO_output", "forward_iteration1_TCO_input", "forward_iteration1_network_outputs_pose"} <= set(got)
+    assert len(got) == 6 + 10 and not any("label" in k or "renders" in k for k in got)
+    assert got["refiner_iteration2_poses"].dtype == np.float32 and np.array_equal(got["refiner_iteration2_poses"], (poses + 2).numpy())
+    assert got["refiner_iteration1_instance_id"].dtype == np.float64 and got["refiner_iteration1_instance_id"].tolist() == [0.0, 7.0]
+    assert got["refiner_iteration1_coarse_logit"].dtype == np.float64
+    assert got["forward_iteration1_network_outputs_pose"].dtype == np.float32
+    monkeypatch.setattr(bench, "DUMP_BUDGET_BYTES", 1024)
+    with pytest.raises(AssertionError):
+        bench.dump_outputs(str(tmp_path / "too_big"), arrays)
+    assert not (tmp_path / "too_big").exists()

@@ -20,7 +20,7 @@ if [ "$WHAT" = "stage" ] || [ "$WHAT" = "all" ]; then
   cp $(find $OUT/st_stats -name p_kernel_stats.csv | head -1) $OUT/stage_kernel_stats.csv
 fi
 if [ "$WHAT" = "bench" ] || [ "$WHAT" = "all" ]; then
-  timeout 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+  timeout 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
   timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o p --output-format csv -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-exact-fp32 --no-extra-workloads > $OUT/prof.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc FETCH_SIZE -d $OUT/trf_fetch -o p --output-format csv -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-extra-workloads > $OUT/trf_fetch.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --pmc WRITE_SIZE -d $OUT/trf_write -o p --output-format csv -- python3 bench.py --steps 4 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-extra-workloads > $OUT/trf_write.log 2>&1

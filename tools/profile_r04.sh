@@ -8,7 +8,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 SHORT="--steps 4 --warmup 1 --no-cpu-baseline --no-exact-fp32 --no-extra-workloads"
 if [ "$WHAT" = "bench" ] || [ "$WHAT" = "all" ]; then
-  timeout 900 python bench.py > $OUT/bench_line.json 2> $OUT/bench.err
+  timeout 900 python bench.py --full > $OUT/bench_line.json 2> $OUT/bench.err
   timeout 600 rocprofv3 --kernel-trace --stats -d $OUT/prof -o p --output-format csv -- python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-exact-fp32 --no-extra-workloads > $OUT/prof.log 2>&1
   cp $(find $OUT/prof -name p_kernel_stats.csv | head -1) $OUT/bench_kernel_stats.csv
 fi

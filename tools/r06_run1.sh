@@ -12,7 +12,7 @@ echo "tests rc=$?"; tail -5 $O/gpu_tests.log
 for rep in 1 2; do
   for v in new pk; do
     if [ $v = pk ]; then export HAPPYPOSE_AMD_LIB=$PWD/happypose_amd/lib_pk/libhappypose_amd.so; else unset HAPPYPOSE_AMD_LIB; fi
-    timeout 400 python bench.py --steps 20 --warmup 3 --no-extra-workloads --no-cpu-baseline --no-exact-fp32 > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err
+    timeout 400 python bench.py --steps 20 --warmup 3 --full --no-extra-workloads --no-cpu-baseline --no-exact-fp32 > $O/bench_${v}_$rep.json 2> $O/bench_${v}_$rep.err
     python - <<P
 import json
 try:

@@ -6,7 +6,7 @@ export PYTHONUNBUFFERED=1
 timeout 300 python bench.py --steps 10 --warmup 3 --no-extra-workloads --no-cpu-baseline --no-exact-fp32 > /dev/null 2>&1   # warm the box
 for rep in 1 2 3 4 5; do
   for g in off on; do
-    timeout 400 python bench.py --steps 30 --warmup 3 --no-extra-workloads --no-cpu-baseline --no-exact-fp32 --graphs $g > $O/bench_graphs_${g}_$rep.json 2> $O/bench_graphs_${g}_$rep.err
+    timeout 400 python bench.py --steps 30 --warmup 3 --full --no-extra-workloads --no-cpu-baseline --no-exact-fp32 --graphs $g > $O/bench_graphs_${g}_$rep.json 2> $O/bench_graphs_${g}_$rep.err
     python3 - <<P
 import json
 try:

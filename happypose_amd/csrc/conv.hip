@@ -290,18 +290,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
         for (int ni = 0; ni < NT; ++ni)
           acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[kg & 1][mi][j], fb[kg & 1][ni][j], acc[mi][ni], 0, 0, 0);
-      // HP_ABL_* are compile-time ablation switches for tools/conv_ablate.sh (which part of the
-      // K loop costs matrix-pipe time); never defined in the product build.
-#ifndef HP_ABL_NO_DSREAD
       if (q == 1) read_frags<MT, NT>(Ab, Bb, 1, fa[1], fb[1]);
       if (q == 5) read_frags<MT, NT>(Ab, Bb, 2, fa[0], fb[0]);
       if (q == 9) read_frags<MT, NT>(Ab, Bb, 3, fa[1], fb[1]);
-#endif
-#ifdef HP_ABL_NO_STAGE
-      if (false) {
-#else
       if (stage) {
-#endif
         if (q < 4) {
 #pragma unroll
           for (int i = q; i < NA; i += 4) load_a_chunk<NA, NB, PRE>(a, e, i, rowoff[i], ih0[i], iw0[i], imgoff[i], st);
@@ -321,9 +313,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
       }
       __builtin_amdgcn_sched_barrier(0);
     }
-#ifndef HP_ABL_NO_BARRIER
     __syncthreads();
-#endif
   }
 
   if (split && !splitk_reduce<BM, BN, MT, NT, kThreads>(a, acc, lin - a.sk_regular, slice)) return;

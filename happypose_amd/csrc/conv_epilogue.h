@@ -81,14 +81,11 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, float* lds, epi
         // the IEEE division was ~10 of the ~15 VALU instructions per stored element, and EfficientNet's wide expansions are
         // bound by exactly those (SQ counters, round 5: VALU active 0.24 of the wave cycles at 3 - 4 waves per SIMD)
       }
-#ifndef HP_EABL_NO_AMAX_VALU
       amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-#endif
       *reinterpret_cast<epi_floatx4*>(a.y + m * a.Cout + n) = v;
     }
   }
   conv_report_nonfinite(a, chk);
-#ifndef HP_EABL_NO_AMAX_REDUCE
   if (a.amax_out) {
     // max is order-independent: deterministic.  The word only grows, so a wave first LOOKS (a plain device-scope load)
     // and sends its atomic only when it would raise the value: after the first few tiles nearly every wave skips it --
@@ -101,7 +98,6 @@ __device__ __forceinline__ void conv_epilogue(const ConvArgs& a, float* lds, epi
       if (mine > __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(slot, mine);
     }
   }
-#endif
 }
 
 }  // namespace hp

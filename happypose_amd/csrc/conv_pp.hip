@@ -41,10 +41,6 @@ typedef _Float16 pp_halfx4 __attribute__((ext_vector_type(4)));
 typedef float pp_floatx16 __attribute__((ext_vector_type(16)));
 typedef float pp_floatx4 __attribute__((ext_vector_type(4)));
 
-#ifdef HP_PP_STAMPS  // diagnostics build: shader cycles and 100-MHz ticks spent in the K loops (-> the shader clock)
-__device__ unsigned long long g_pp_stamps[8];
-#endif
-
 int conv_num_cus() {  // of the current device (queried once: one device per process, as everywhere in this library)
   static const int cus = [] {
     int dev = 0, n = 256;
@@ -177,17 +173,7 @@ __device__ __forceinline__ void pp_epilogue_direct(const ConvArgs& a, pp_floatx1
             chk += (v[0] + v[1]) + (v[2] + v[3]);
             if (a.relu == HP_ACT_RELU) v = __builtin_elementwise_max(v, pp_floatx4{0.f, 0.f, 0.f, 0.f});
             amax = fmaxf(amax, fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3]))));
-#if defined(HP_PP_NT_STORES)   // experiment: non-temporal output stores
-            __builtin_nontemporal_store(v, reinterpret_cast<pp_floatx4*>(a.y + m * a.Cout + n));
-#elif defined(HP_PP_SC1_STORES)  // experiment: write-through (sc1) output stores
-            {
-              typedef unsigned int pp_uintx4 __attribute__((ext_vector_type(4)));
-              const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, 0x7FFFFFFF, 0x00020000);
-              __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(pp_uintx4, v), yr, (int)((m * a.Cout + n) * 4), 0, 16);
-            }
-#else
             *reinterpret_cast<pp_floatx4*>(a.y + m * a.Cout + n) = v;
-#endif
           }
         }
       }
@@ -276,9 +262,6 @@ __global__ __launch_bounds__(kPPThreads) __attribute__((amdgpu_waves_per_eu(2, 2
   // stalled the whole phase for an HBM / L2 round trip: 1918 instead of 1690 cycles per tap on the PRE layers)
   float* const pre_lds = reinterpret_cast<float*>(zrow + LDH);      // split: [Cin] scale, [Cin] shift (fp32); f16: halves
 
-#ifdef HP_PP_STAMPS
-  const unsigned long long st_k0 = __builtin_readcyclecounter();
-#endif
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
   const int W = a.W, H = a.H, Cin = a.Cin;
   const int ncc_all = Cin / CKC;
@@ -576,9 +559,6 @@ __global__ __launch_bounds__(kPPThreads) __attribute__((amdgpu_waves_per_eu(2, 2
   if (have) issue_first_loads();
   while (have) {
     // ---- prologue of `cur`: its first loads are in flight (issued above, or before the previous item's epilogue)
-#ifdef HP_PP_STAMPS
-    const unsigned long long st_p0 = __builtin_readcyclecounter();
-#endif
 #pragma unroll
     for (int i = 0; i < MT; ++i)
 #pragma unroll
@@ -589,9 +569,6 @@ __global__ __launch_bounds__(kPPThreads) __attribute__((amdgpu_waves_per_eu(2, 2
     store_b(0, 0);
     load_b(0, cc_begin, 2);
     __syncthreads();
-#ifdef HP_PP_STAMPS
-    const unsigned long long st_t0 = __builtin_readcyclecounter(), st_r0 = __builtin_amdgcn_s_memrealtime();
-#endif
     if (odd) __builtin_amdgcn_s_barrier();
     int cc = cc_begin;
     for (; cc + 1 < ncc; cc += 2) {
@@ -600,17 +577,6 @@ __global__ __launch_bounds__(kPPThreads) __attribute__((amdgpu_waves_per_eu(2, 2
     }
     if (cc < ncc) chunk(cc, std::integral_constant<int, 0>{});
     if (!odd) __builtin_amdgcn_s_barrier();  // both wave groups are past their last fragment reads: the LDS buffers are free
-#ifdef HP_PP_STAMPS
-    if (tid == 0) {
-      atomicAdd(&g_pp_stamps[0], __builtin_readcyclecounter() - st_t0);
-      atomicAdd(&g_pp_stamps[1], __builtin_amdgcn_s_memrealtime() - st_r0);
-      atomicAdd(&g_pp_stamps[2], (unsigned long long)((ncc - cc_begin) * 9));
-      atomicAdd(&g_pp_stamps[3], 1ull);
-      atomicAdd(&g_pp_stamps[4], st_t0 - st_p0);  // prologue of this item (waiting for its prefetched loads, staging)
-      if (vb == (int)blockIdx.x) atomicAdd(&g_pp_stamps[6], st_p0 - st_k0);  // per-workgroup set-up before the first item
-    }
-    const unsigned long long st_e0 = __builtin_readcyclecounter();
-#endif
     // ---- the next item's loop state and first loads, then this item's epilogue (whose stores drain under the next K loop)
     Item nxt{};
     vb += (int)gridDim.x;
@@ -628,9 +594,6 @@ __global__ __launch_bounds__(kPPThreads) __attribute__((amdgpu_waves_per_eu(2, 2
                                    WIDE ? 0 : (wave_ & 1) * (BN / 2), act_inv, t_ & 63, prefetch_next);
     }
     if (!issued) prefetch_next();
-#ifdef HP_PP_STAMPS
-    if (tid == 0) atomicAdd(&g_pp_stamps[5], __builtin_readcyclecounter() - st_e0);  // slab hand-off + epilogue issue
-#endif
     cur = nxt;
   }
 }
@@ -1091,12 +1054,3 @@ int launch_conv_pp_f16(const ConvArgsH& h, hipStream_t stream) {
 
 }  // namespace hp
 
-#ifdef HP_PP_STAMPS
-extern "C" __attribute__((visibility("default"))) int hp_debug_pp_stamps(double* out4) {  // cycles, 100-MHz ticks, taps, workgroups, prologue cycles, epilogue cycles
-  unsigned long long h[8], z[8] = {0, 0, 0, 0, 0, 0, 0, 0};
-  if (hipMemcpyFromSymbol(h, HIP_SYMBOL(hp::g_pp_stamps), sizeof(h)) != hipSuccess) return -1;
-  (void)hipMemcpyToSymbol(HIP_SYMBOL(hp::g_pp_stamps), z, sizeof(z));
-  for (int i = 0; i < 7; ++i) out4[i] = (double)h[i];
-  return 0;
-}
-#endif

@@ -246,7 +246,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) __attribute__((amdgpu_waves
   load_b(0, cc_begin * 9 + 2);
   __syncthreads();
 
-#ifndef HP_SPLIT_OLD_TAP
   // ---- software-pipelined tap body.  A tap is six groups of MT x NT MFMAs (hi.hi, hi.lo, lo.hi for each of the two
   // 16-channel k-steps).  The fragments of group g + 1 are read BEFORE the MFMAs of group g are issued, the first
   // group's fragments of the NEXT tap before the last group of this one, and the per-tap barrier sits between groups
@@ -335,109 +334,6 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) __attribute__((amdgpu_waves
     }
   };
 #undef HP_PIN
-#else
-  auto tap_step = [&](int tt, int cc, int tap, auto par) {
-    constexpr int Pb = decltype(par)::value;  // tt & 1: LDS weight buffer of this tap
-    const int d = (tap / 3 - 1) * W + (tap % 3 - 1);
-    // rows whose shifted pixel lies across an image border read the zero row instead
-    const _Float16* Ab[MT];
-#pragma unroll
-    for (int i = 0; i < MT; ++i) {
-#ifndef HP_SABL_NOMASK
-      Ab[i] = ((vmask[i] >> tap) & 1u) ? Afr[i] + d * LDH : Zfr;
-#else
-      Ab[i] = Afr[i] + d * LDH;
-#endif
-    }
-    const _Float16* Bb = Bfr + Pb * BN * LDH;
-    const bool next_chunk = cc + 1 < ncc;
-    // fragment q of a row: 0 / 1 = hi halves of channels 0-15 / 16-31, 2 / 3 = their lo halves
-    auto read_a = [&](halfx8 (&f)[MT], int q) {
-#pragma unroll
-#ifdef HP_SABL_NOREAD
-      for (int i = 0; i < MT; ++i) f[i] = __builtin_bit_cast(halfx8, floatx4{(float)tt, (float)q, 1.f, 2.f});
-#else
-      for (int i = 0; i < MT; ++i) f[i] = *reinterpret_cast<const halfx8*>(Ab[i] + q * 16);
-#endif
-    };
-    auto read_b = [&](halfx8 (&f)[NT], int q) {
-#pragma unroll
-#ifdef HP_SABL_NOREAD
-      for (int i = 0; i < NT; ++i) f[i] = __builtin_bit_cast(halfx8, floatx4{(float)tt, (float)q, 3.f, 4.f});
-#else
-      for (int i = 0; i < NT; ++i) f[i] = *reinterpret_cast<const halfx8*>(Bb + i * 32 * LDH + q * 16);
-#endif
-    };
-    auto mm = [&](const halfx8 (&fa)[MT], const halfx8 (&fb)[NT]) {
-#pragma unroll
-      for (int mi = 0; mi < MT; ++mi)
-#pragma unroll
-        for (int ni = 0; ni < NT; ++ni)
-          acc[mi][ni] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fa[mi], fb[ni], acc[mi][ni], 0, 0, 0);
-    };
-    // six groups of MT x NT MFMAs; a fragment set is read one group before its first use and is dead after
-    // its second (hi) or only (lo) use: at most five sets are live
-    halfx8 ah[MT], al[MT], bh[NT], bl[NT], ah1[MT], bh1[NT];
-    // (the staging below is unconditional -- clamped addresses, a dead LDS buffer after the last tap -- so
-    // that the tap body is straight-line code: with branches the compiler waits for ALL outstanding loads)
-    read_a(ah, 0);
-    read_b(bh, 0);
-    read_b(bl, 2);
-#ifndef HP_SABL_NOBSTAGE
-#ifndef HP_SABL_NOBSTORE
-    store_b(1 - Pb, 1 - Pb);               // weights of tap tt+1 (register set (tt+1) & 1)
-#endif
-#ifndef HP_SABL_NOBLOAD
-    load_b(1 - Pb, tt + 3);                // ... and that set takes tap tt+3
-#endif
-#endif
-#ifdef HP_SPLIT_2BATCH
-    halfx8 al1[MT], bl1[NT];
-    read_a(al, 2);
-    mm(ah, bh);
-    read_a(ah1, 1);
-    read_b(bh1, 1);
-    read_b(bl1, 3);
-    read_a(al1, 3);
-    mm(ah, bl);
-    mm(al, bh);
-#ifndef HP_SABL_NOPATCH
-#pragma unroll
-    for (int j = 0; j < NPC; ++j)          // next chunk's patch: one pass per tap (taps 0 .. NPC-1)
-      if (j == tap) load_patch(j, cc + 1 < ncc ? cc + 1 : cc);
-#endif
-    mm(ah1, bh1);
-    mm(ah1, bl1);
-    mm(al1, bh1);
-#else
-    mm(ah, bh);
-    read_a(al, 2);
-    mm(ah, bl);
-    read_a(ah1, 1);
-    read_b(bh1, 1);
-    mm(al, bh);
-    read_b(bl, 3);
-#ifndef HP_SABL_NOPATCH
-#pragma unroll
-    for (int j = 0; j < NPC; ++j)          // next chunk's patch: one pass per tap (taps 0 .. NPC-1)
-      if (j == tap) load_patch(j, cc + 1 < ncc ? cc + 1 : cc);
-#endif
-    mm(ah1, bh1);
-    read_a(al, 3);
-    mm(ah1, bl);
-    mm(al, bh1);
-#endif
-#ifndef HP_SABL_NOBARRIER
-    __syncthreads();
-#endif
-#ifndef HP_SABL_NOPATCH
-    if (tap == 8 && next_chunk) {  // every wave is done with this chunk's patch: swap in the next one
-      store_patch(cc + 1);
-      __syncthreads();
-    }
-#endif
-  };
-#endif
   // tap t of the item's chunk number rc uses weight buffer (rc + t) & 1: two chunks per loop iteration make
   // that a compile-time value
   auto chunk = [&](int cc, auto c0) {
@@ -449,26 +345,14 @@ __global__ __launch_bounds__(64 * WAVES_M * WAVES_N) __attribute__((amdgpu_waves
     tap_step(cc * 9 + 6, cc, 6, E{}); tap_step(cc * 9 + 7, cc, 7, O{}); tap_step(cc * 9 + 8, cc, 8, E{});
   };
   int cc = cc_begin;
-#ifndef HP_SPLIT_OLD_TAP
   prefetch_first(0, 0);
-#endif
-#ifdef HP_SABL_NOLOOP
-  cc = ncc;
-#endif
   for (; cc + 1 < ncc; cc += 2) {
     chunk(cc, std::integral_constant<int, 0>{});
     chunk(cc + 1, std::integral_constant<int, 1>{});
   }
   if (cc < ncc) chunk(cc, std::integral_constant<int, 0>{});
 
-#ifdef HP_SPLIT_FENCED_SLABS
-  if (split && !splitk_reduce<BM, BN, MT, NT, kThreads>(a, acc, lin - a.sk_regular, slice)) return;
-#else
   if (split && !splitk_reduce_sc1<BM, BN, MT, NT, kThreads>(a, acc, lin - a.sk_regular, slice)) return;
-#endif
-#ifdef HP_SABL_NOEPI
-  if (acc[0][0][0] != 12345.f) return;
-#endif
 
   // ---- scale back (a lane holds one output channel per N tile), then the shared fp32 epilogue
   const float* const unscale = reinterpret_cast<const float*>(reinterpret_cast<const _Float16*>(a.w) + (size_t)a.Cout * 18 * Cin);

@@ -440,13 +440,6 @@ __global__ __launch_bounds__(s7p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
                      // record could be composed in registers and stored as three ds_write_b64 -- cost 450 us per launch: TA-bound)
   auto issue_loads = [&](const Tile& ts) {
     if (!ts.ok) return;
-#ifdef HP_S7_ABL_NOLOAD
-    if (a.M > 0) {
-#pragma unroll
-      for (int k = 0; k < NIT; ++k) { sv[k] = uintx4{0u, 0u, 0u, 0u}; sw[k] = 0u; }
-      return;
-    }
-#endif
     const int ih_base = 2 * (2 * PR * ts.ty - 1) - 3, iw_base = 2 * (2 * PC * ts.tx - 1) - 3;
     const _Float16* const ximg = xg + (int64_t)ts.img * H * W * 16;
 #pragma unroll
@@ -482,14 +475,8 @@ __global__ __launch_bounds__(s7p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
       for (int nt = 0; nt < 2; ++nt)
         wt[slot][nt] = *reinterpret_cast<const s7_halfx8*>(Wl + (kh * BN + 32 * nt) * WROWB + aoff + 32 * kk);
     };
-#ifdef HP_S7_ABL_NOMFMA  // diagnostics builds (tools/stem_ablate.sh): phases compiled out
-    const bool mm_on = t.ok && a.M < 0;
-#else
     const bool mm_on = t.ok;
-#endif
-#ifndef HP_S7_ABL_NOPRIO
     __builtin_amdgcn_s_setprio(3);  // the multiplying wave goes first on its SIMD (its partner is in the O role)
-#endif
     if (mm_on) { fetch(0, 0); fetch(1, 1); }
 #pragma unroll
     for (int st = 0; st < NSTEP; ++st) {
@@ -505,20 +492,14 @@ __global__ __launch_bounds__(s7p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
       }
       if (st == 4 * KSTEPS - 1) lds_barrier();  // the O group's mid-phase barrier
     }
-#ifndef HP_S7_ABL_NOPRIO
     __builtin_amdgcn_s_setprio(0);
-#endif
     lds_barrier();
   };
 
   auto role_o = [&](const Tile& te, const Tile& ts, bool load_now) {
     if (load_now) issue_loads(ts);
     // ---- pooled epilogue of the tile this group multiplied in the previous phase
-#ifdef HP_S7_ABL_NOEPI
-    if (te.ok && a.M < 0) {
-#else
     if (te.ok) {
-#endif
       unsigned char* const Ew = Grp + wl * 64 * EPITCH;
       const int oh0 = 2 * PR * te.ty - 1, ow0 = 2 * PC * te.tx - 1 + 8 * wl;
 #pragma unroll

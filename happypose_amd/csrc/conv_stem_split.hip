@@ -213,11 +213,9 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
 // pixels, the MFMAs run transposed (weights as A: a lane holds one pixel and 16 consecutive couts), scale-back + bias + ReLU
 // happen in registers (all monotone, so they commute with the max: same values as the tile kernel, same MFMA order), the
 // tile goes to LDS 32 couts at a time and the wave pools what it wrote itself.  The epilogue tile aliases the group's input.
-#ifndef HP_S5_MID_KT
-#define HP_S5_MID_KT 3
-#endif
 namespace s5p {
 constexpr int kT = 512;
+constexpr int MID_KT = 3;                     // the M role's k-step that meets the O group's mid-phase barrier
 constexpr int ROWP2 = 424;                    // halves per staged input row: 416 + 8 (424 mod 64 = 40: see kRowPix)
 constexpr int PLANE2 = IR * ROWP2;            // halves per plane
 constexpr int IN_BYTES = 2 * PLANE2 * 2;      // hi + lo planes
@@ -301,13 +299,6 @@ __global__ __launch_bounds__(s5p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
   floatx4 sv[NIT];  // the group's next tile: 16-B chunks of its input region (fp32), issued at the head of the M role
   auto issue_loads = [&](const Tile& ts) {
     if (!ts.ok) return;
-#ifdef HP_S5_ABL_NOLOAD
-    if (a.M > 0) {
-#pragma unroll
-      for (int k = 0; k < NIT; ++k) sv[k] = floatx4{0.f, 0.f, 0.f, 0.f};
-      return;
-    }
-#endif
     const int ih_base = 2 * (2 * PR * ts.ty - 1) - 2, fl_base = (2 * (2 * PC * ts.tx - 1) - 2) * 6;
     const float* const ximg = a.x + (int64_t)ts.img * H * W * 6;
     int g_ = gt;
@@ -358,11 +349,7 @@ __global__ __launch_bounds__(s5p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
           acc[mt][nt] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[sl][nt], xl[sl][mt], acc[mt][nt], 0, 0, 0);
         }
     };
-#ifdef HP_S5_ABL_NOMFMA  // diagnostics builds (tools/stem_ablate.sh): phases compiled out
-    const bool mm_on = t.ok && a.M < 0;
-#else
     const bool mm_on = t.ok;
-#endif
     if (mm_on) fetch(0, 0);
 #pragma unroll 1
     for (int kt = 0; kt < KT; ++kt) {  // two k-steps per filter row; rolled: unrolled ten times the addresses of all steps stay live
@@ -380,7 +367,7 @@ __global__ __launch_bounds__(s5p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
       }
       // the O group's mid-phase barrier, LATE in the M role: its first half (the fp32 epilogue through LDS) is the long one,
       // its second (hi / lo split + store of the staged chunks) short
-      if (kt == HP_S5_MID_KT) lds_barrier();
+      if (kt == MID_KT) lds_barrier();
     }
     __builtin_amdgcn_s_setprio(0);
     lds_barrier();
@@ -388,11 +375,7 @@ __global__ __launch_bounds__(s5p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 
   auto role_o = [&](const Tile& te, const Tile& ts, bool load_now) {
     if (load_now) issue_loads(ts);
-#ifdef HP_S5_ABL_NOEPI
-    if (te.ok && a.M < 0) {
-#else
     if (te.ok) {
-#endif
       unsigned char* const Ew = Grp + wl * 64 * EPITCH;
       const int oh0 = 2 * PR * te.ty - 1, ow0 = 2 * PC * te.tx - 1 + 8 * wl;
 #pragma unroll

@@ -107,14 +107,6 @@ __device__ __forceinline__ floatx4 sub4(floatx4 a, floatx4 b) {
   return floatx4{lo.x, lo.y, hi.x, hi.y};
 }
 
-#ifdef HP_WABL_TIMING  // per-block time stamps (diagnostic build only): [block][0 start, 1 first K loop, 2+i end of item i]
-constexpr int kStampSlots = 64;
-__device__ long long g_wino_stamps[512 * kStampSlots];
-#define HP_STAMP(slot) do { if (threadIdx.x == 0 && (slot) < kStampSlots) g_wino_stamps[blockIdx.x * kStampSlots + (slot)] = wall_clock64(); } while (0)
-#else
-#define HP_STAMP(slot) do { } while (0)
-#endif
-
 __device__ __forceinline__ floatx2 add2(floatx2 a, floatx2 b) {
   floatx2 r;
   asm("v_pk_add_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
@@ -159,11 +151,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
   const int kg = lane >> 4;
   const int H = a.H, W = a.W, Cin = a.Cin;
   const int nchunks = Cin / CK;
-  HP_STAMP(0);
-#ifdef HP_WABL_TIMING
-  int stamp_slot = 2;
-  if (threadIdx.x == 0) g_wino_stamps[blockIdx.x * kStampSlots + 62] = clock64();  // shader-clock counter at the start
-#endif
   const int c4 = tid & 3, srow = tid >> 2;  // channel quad / first pixel row this thread stages
   if (tid < 16) rawl[((tid >> 2) * Pp + Pmax) * 4 + (tid & 3)] = 0.f;
 
@@ -309,14 +296,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
 #pragma unroll
     for (int j = 0; j < 4; ++j)
       t[j] = i == 0 ? sub4(d[0 + j], d[8 + j]) : i == 1 ? d[4 + j] + d[8 + j] : i == 2 ? sub4(d[8 + j], d[4 + j]) : sub4(d[4 + j], d[12 + j]);
-#ifdef HP_WABL_NO_XFORM
-    V[4 * i + 0] = d[4 * i + 0]; V[4 * i + 1] = d[4 * i + 1]; V[4 * i + 2] = d[4 * i + 2]; V[4 * i + 3] = d[4 * i + 3];
-#else
     V[4 * i + 0] = sub4(t[0], t[2]);
     V[4 * i + 1] = t[1] + t[2];
     V[4 * i + 2] = sub4(t[2], t[1]);
     V[4 * i + 3] = sub4(t[1], t[3]);
-#endif
   };
   setup_tile(item);
   setup_doff(0);
@@ -324,14 +307,10 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
   read_d_rows(rawl, 0, 2);
   read_d_rows(rawl, 1, 3);
   __syncthreads();  // every wave holds its pixels of chunk 0: the pixel buffer may be refilled
-  HP_STAMP(1);
 
   for (;;) {
     const int bm = fdiv(item, fd.tn), n0 = (item - bm * tiles_n) * BN;
     const bool has_next = item + nslot < item_end;
-#ifdef HP_WABL_TIMING
-    HP_STAMP(stamp_slot);  // K loop starts
-#endif
     floatx4 acc[16][2];
 #pragma unroll
     for (int p = 0; p < 16; ++p)
@@ -345,9 +324,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     auto chunk = [&](int c, auto odd, auto is_last) {
       constexpr std::integral_constant<int, 1 - decltype(odd)::value> nxt{};
       constexpr bool LAST = decltype(is_last)::value;
-#ifdef HP_WABL_TIMING
-      if (stamp_slot == 5) HP_STAMP(32 + c);  // chunk starts of the block's second item
-#endif
       // One chunk = 16 steps (one transform position each: 2 weight fragment reads for the next
       // step, 8 MFMAs), with the rest of the work dealt out between them so that the matrix pipe
       // never waits: input transform rows 1-3 under steps 0/4/8, the next stage's LDS stores under
@@ -369,15 +345,11 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
         if (p == 0) xform_row(1);
         if (p == 4) xform_row(2);
         if (p == 8) xform_row(3);
-#if !defined(HP_WABL_NO_STAGE) && !defined(HP_WABL_NO_LSTORE)
         if (p < 8) store_held(nxt, ubuf ^ 1, p);
-#endif
-#if !defined(HP_WABL_NO_STAGE) && !defined(HP_WABL_NO_GLOAD)
         if (p >= 8) {  // registers of the stage just stored are free: stage + 3 pixels, stage + 2 weights
           issue_raw(nxt, p - 8);
           issue_u(p - 8);
         }
-#endif
         // the last chunk of an item sets up the tile of the NEXT item (its first stage is what the
         // barrier below publishes), so an item boundary costs no pixel-read latency
         // (after the block's last item: the same item again, read and never used)
@@ -386,34 +358,23 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
           if (p == 10) setup_doff(0);
           if (p == 11) setup_doff(1);
         }
-        if (p == 12) {
-#ifndef HP_WABL_NO_BARRIER
-          __syncthreads();  // the next stage is in LDS
-#endif
-
-        }
-#ifndef HP_WABL_NO_READD
+        if (p == 12) __syncthreads();  // the next stage is in LDS
         if (p == 12) read_d_rows(rawl, 0, 0);
         if (p == 13) read_d_rows(rawl, 2, 2);
         if (p == 14) read_d_rows(rawl, 1, 1);
         if (p == 15) read_d_rows(rawl, 3, 3);
-#endif
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
           for (int nt = 0; nt < 2; ++nt)
             acc[p][nt] = __builtin_amdgcn_mfma_f32_16x16x4f32(V[p][j], bf[p & 1][nt][j], acc[p][nt], 0, 0, 0);
-#ifndef HP_WABL_NO_PIN
         __builtin_amdgcn_sched_barrier(0);
-#endif
       }
       ubuf ^= 1;
-#ifndef HP_WABL_NO_BARRIER
       // every wave holds its pixels of chunk c+1 and is done with this chunk's weights: both
       // buffers may be refilled (a third weight buffer + a second pixel buffer would save this
       // barrier, but the 60x80 layers have no LDS left for them)
       __syncthreads();
-#endif
     };
     for (int c = 0; c + 2 < nchunks; c += 2) {
       chunk(c, SET_A, std::false_type{});
@@ -421,9 +382,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
     }
     chunk(nchunks - 2, SET_A, std::false_type{});
     chunk(nchunks - 1, SET_B, std::true_type{});
-#ifdef HP_WABL_TIMING
-    HP_STAMP(stamp_slot + 1);  // K loop done
-#endif
     // ---- output transform Y = A^T M A per (tile row i of the lane, cout tile), epilogue.
     //      A lane holds the 2x2 pixels of ONE cout; a 4x4 transpose inside each lane quad (two
     //      DPP butterfly stages) turns that into 4 consecutive couts of ONE pixel, so bias,
@@ -478,11 +436,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
           if (hi) { y[0] = x0; y[1] = x1; } else { y[2] = x0; y[3] = x1; }
         }
         // y[c] = pixel lq, cout ncol + nt*16 + c
-#ifdef HP_WABL_NO_EPI
-        if (ok && y[0] == 123.456f) {
-#else
         if (ok) {
-#endif
           floatx4 v = {y[0], y[1], y[2], y[3]};
           if (a.bias) v += *reinterpret_cast<const floatx4*>(a.bias + ncol + nt * 16);
           if (a.residual) v += *reinterpret_cast<const floatx4*>(a.residual + obase + nt * 16);
@@ -497,11 +451,6 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(1, 1))
         __builtin_amdgcn_sched_barrier(0);
       }
     }
-#ifdef HP_WABL_TIMING
-    HP_STAMP(stamp_slot + 2);  // epilogue done
-    if (stamp_slot == 2 && threadIdx.x == 0) g_wino_stamps[blockIdx.x * kStampSlots + 63] = clock64();  // ... and after item 0
-    stamp_slot += 3;
-#endif
     item += nslot;
     if (item >= item_end) break;
   }
@@ -561,11 +510,6 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
   const int kg = lane >> 4;
   const int H = a.H, W = a.W, Cin = a.Cin;
   const int nchunks = Cin / CK;
-  HP_STAMP(0);
-#ifdef HP_WABL_TIMING
-  int stamp_slot = 2;
-  if (threadIdx.x == 0) g_wino_stamps[blockIdx.x * kStampSlots + 62] = clock64();
-#endif
   const int c4 = tid & 3, srow = tid >> 2;  // channel quad / first pixel row this thread stages
   if (tid < 16) rawl[((tid >> 2) * Pp + ZS) * 4 + (tid & 3)] = 0.f;
   if (PRE) {  // the prologue constants live in LDS: held in registers they would stay live across the epilogue
@@ -706,10 +650,6 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
     for (int p = p0; p < p1; ++p) d[p] = *reinterpret_cast<const floatx4*>(rawl + doff[p]);
   };
   auto col_xform = [&](const floatx4 (&t)[4], int row) {
-#ifdef HP_WABL_NO_XFORM
-    V[4 * row + 0] = t[0]; V[4 * row + 1] = t[1]; V[4 * row + 2] = t[2]; V[4 * row + 3] = t[3];
-    return;
-#endif
     V[4 * row + 0] = sub4s(t[0], t[2]);
     V[4 * row + 1] = add4s(t[1], t[2]);
     V[4 * row + 2] = sub4s(t[2], t[1]);
@@ -722,22 +662,14 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
     floatx4 t[4];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-#ifdef HP_WABL_NO_XFORM
-      t[j] = d[0 + j];
-#else
       t[j] = sub4s(d[0 + j], d[8 + j]);
-#endif
     }
     col_xform(t, 0);
   };
   auto xform_second_rows = [&]() {  // needs E1, E2; both die
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-#ifdef HP_WABL_NO_XFORM
-      tS[j] = d[4 + j];
-#else
       tS[j] = pk_fma4(d[8 + j], s_second2, d[4 + j]);
-#endif
     }
   };
   auto xform_second = [&]() { col_xform(tS, 1); };
@@ -750,15 +682,11 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
   xform_first();
   xform_second_rows();
   __syncthreads();  // every wave holds its pixels of chunk 0: the pixel buffer may be refilled
-  HP_STAMP(1);
 
   for (;;) {
     const int bm = fdiv(real_item(item), fd.tn), n0 = (real_item(item) - bm * tiles_n) * BN;
     const bool has_next = item + nslot < item_end;
     const int hoff = half_off(item), hoff_next = half_off(has_next ? item + nslot : item);
-#ifdef HP_WABL_TIMING
-    HP_STAMP(stamp_slot);
-#endif
     floatx4 acc[8][NT];
 
     // one chunk = 8 steps (one position each: 2 weight-fragment reads for the next step, 8 MFMAs);
@@ -770,9 +698,6 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
       constexpr std::integral_constant<int, 1 - decltype(odd)::value> nxt{};
       constexpr bool FIRST = decltype(is_first)::value;
       constexpr bool LAST = decltype(is_last)::value;
-#ifdef HP_WABL_TIMING
-      if (stamp_slot == 5) HP_STAMP(32 + c);
-#endif
       const float* ub_lo = ufr_lo + ubuf * U_BUF + hoff;
       const float* ub_hi = ufr_hi + ubuf * U_BUF + hoff;
       // bf[0] and V[0..3] of this chunk were prepared under the last step of the previous one (the
@@ -789,27 +714,19 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
             bf[0][nt] = *reinterpret_cast<const floatx4*>(ufr_lo + (ubuf ^ 1) * U_BUF + (LAST ? hoff_next : hoff) + nt * 16 * 4);
         }
         if (q == 0) xform_second();
-#if !defined(HP_WABL_NO_STAGE) && !defined(HP_WABL_NO_LSTORE)
         if (q < 4) store_held(nxt, ubuf ^ 1, q);
-#endif
-#if !defined(HP_WABL_NO_STAGE) && !defined(HP_WABL_NO_GLOAD)
         if (q >= 4) {
           issue_raw(nxt, q - 4);
           issue_u(q - 4);
         }
-#endif
         if (LAST) {  // tile of the NEXT item (after the block's last item: the same again, never used)
           if (q == 2) setup_tile(has_next ? item + nslot : item);
           if (q == 3) setup_doff();
         }
-#ifndef HP_WABL_NO_BARRIER
         if (q == 4) __syncthreads();  // the next stage is in LDS
-#endif
-#ifndef HP_WABL_NO_READD
         if (q == 4) read_d(0, 4);     // E0
         if (q == 5) read_d(8, 12);    // E2
         if (q == 6) read_d(4, 8);     // E1
-#endif
 #pragma unroll
         for (int j = 0; j < 4; ++j)
 #pragma unroll
@@ -824,9 +741,7 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
         __builtin_amdgcn_sched_barrier(0);
       }
       ubuf ^= 1;
-#ifndef HP_WABL_NO_BARRIER
       __syncthreads();  // pixels of the next chunk held by every wave, this chunk's weights consumed
-#endif
     };
     constexpr std::false_type NO{};
     constexpr std::true_type YES{};
@@ -838,9 +753,6 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
     }
     chunk(nchunks - 2, SET_A, NO, NO);
     chunk(nchunks - 1, SET_B, NO, YES);
-#ifdef HP_WABL_TIMING
-    HP_STAMP(stamp_slot + 1);
-#endif
 
     // ---- where the lane's results go.  The weights are the A operand of the MFMAs, so a lane's four
     //      accumulator elements are 4 CONSECUTIVE COUTS (4 kg .. 4 kg + 3 of the 16-cout tile) of ONE
@@ -941,11 +853,6 @@ __global__ __launch_bounds__(kThreads8) __attribute__((amdgpu_waves_per_eu(2, 2)
         *reinterpret_cast<floatx4*>(a.y + e_off[i]) = v;
       }
     }
-#ifdef HP_WABL_TIMING
-    HP_STAMP(stamp_slot + 2);
-    if (stamp_slot == 2 && threadIdx.x == 0) g_wino_stamps[blockIdx.x * kStampSlots + 63] = clock64();
-    stamp_slot += 3;
-#endif
     item += nslot;
     if (item >= item_end) break;
   }
@@ -1136,8 +1043,3 @@ int launch_conv_wino(const ConvArgs& a, hipStream_t stream) {
 
 }  // namespace hp
 
-#ifdef HP_WABL_TIMING
-extern "C" int hp_debug_wino_stamps(long long* out, int n) {
-  return hipMemcpyFromSymbol(out, HIP_SYMBOL(hp::g_wino_stamps), sizeof(long long) * n) == hipSuccess ? 0 : -1;
-}
-#endif

@@ -29,13 +29,6 @@
 #include "common.h"
 #include "crop_math.h"
 
-#ifndef HP_RASTER_BAND_PIXELS
-#define HP_RASTER_BAND_PIXELS 3200
-#endif
-#ifndef HP_RASTER_THREADS
-#define HP_RASTER_THREADS 512
-#endif
-
 namespace hp {
 
 #pragma clang fp contract(off)
@@ -46,17 +39,14 @@ constexpr int kSub = 256;                  // sub-pixel grid of the snapped vert
 constexpr float kGuardSub = 4194304.0f;    // guard band: +-2^22 sub-pixel units = +-16384 px
 constexpr int kSmallLimit = 8192;          // |corner - origin| <= 32 px on both axes: 32-bit edge functions (v_mad_i32_i24)
 constexpr unsigned long long kKeyEmpty = 0xFFFFFFFFFFFFFFFFull;
-constexpr int kBandPixels = HP_RASTER_BAND_PIXELS;  // LDS z-buffer of a band, 8 B per pixel
+constexpr int kBandPixels = 3200;  // LDS z-buffer of a band, 8 B per pixel
 // HP_RASTER_MSAA4 (the reference's framebuffer state, see oracle.c HP_R_MSAA4): five keys per pixel -- the four colour
 // samples of the standard 4x pattern and the pixel centre (depth / mask stay centre-sampled) -- in a 25-KB z-buffer:
 // 2 rows of 320 pixels per band, four 256-thread workgroups per CU (band_threads below); renders wider than 640 px take
 // 512 threads on 6400 keys.
 constexpr int kSamplesMsaa = 5;
-#ifndef HP_RASTER_BAND_KEYS_MSAA
-#define HP_RASTER_BAND_KEYS_MSAA 3200
-#endif
 constexpr int kMaxViews = 8;  // views per item a record layout can describe
-constexpr int kBandKeysMsaa = HP_RASTER_BAND_KEYS_MSAA;
+constexpr int kBandKeysMsaa = 3200;
 constexpr int kBandKeysMsaaWide = 6400;
 // The renderer conventions nobody can pin without Panda3D (hp_raster_conventions in the header), as the kernels see them:
 // the store's record plus what the host derives from it once per launch.  Kernel arguments (SGPRs).
@@ -83,11 +73,8 @@ __device__ __forceinline__ void aniso_footprint(const CV& cv, float pmax, float 
 constexpr int kBigQueue = 512;
 constexpr int kBigArea = 128;  // candidate pixels above which a triangle is walked cooperatively
 constexpr int kSmallArea = 6;  // ... up to which a record goes to the front of its band's list (raster_setup_kernel)
-#ifndef HP_RASTER_THREADS_MSAA
-#define HP_RASTER_THREADS_MSAA 256
-#endif
 // NS: keys per pixel (1 / 5); WIDE: the multisampled instantiation for renders wider than 640 px (512 threads, 6400 keys)
-constexpr __host__ __device__ int band_threads(int ns, bool wide = false) { return ns == 1 ? HP_RASTER_THREADS : wide ? 512 : HP_RASTER_THREADS_MSAA; }
+constexpr __host__ __device__ int band_threads(int ns, bool wide = false) { return ns == 1 || wide ? 512 : 256; }
 constexpr int kBinThreads = 256;   // set-up kernel: small workgroups (six per CU) -- a 1024-thread workgroup left one per CU waiting at its barriers (66 us per 128 views instead of ~25)
 constexpr int kMaxBands = 768;  // 720 one-row multisampled bands of a 1280 x 720 render
 
@@ -264,17 +251,7 @@ __device__ __forceinline__ BiTapP2 bi_setup_p2(int qoff, int w, int h, float u, 
 }
 typedef uint32_t u32x4_a8 __attribute__((ext_vector_type(4), aligned(8)));
 __device__ __forceinline__ BiTexels bi_load_p2(const uint8_t* texq, const BiTapP2& t) {
-#if defined(HP_TEXQ_4X4)
-  const uint32_t* const qp = reinterpret_cast<const uint32_t*>(texq + t.o);
-  struct { uint32_t x, y, z, w; } q{qp[0], qp[1], qp[2], qp[3]};
-  asm volatile("" ::: "memory");
-#elif defined(HP_TEXQ_2X8)
-  typedef uint32_t u32x2_a8 __attribute__((ext_vector_type(2), aligned(8)));
-  const u32x2_a8 qa = *reinterpret_cast<const u32x2_a8*>(texq + t.o), qb = *reinterpret_cast<const u32x2_a8*>(texq + t.o + 8);
-  struct { uint32_t x, y, z, w; } q{qa.x, qa.y, qb.x, qb.y};
-#else
   const u32x4_a8 q = *reinterpret_cast<const u32x4_a8*>(texq + t.o);  // the whole 2 x 2 footprint: one 16-B load, 8-B aligned
-#endif
   BiTexels r;
   auto px = [](uint32_t v) { return make_uchar4((unsigned char)(v & 255u), (unsigned char)((v >> 8) & 255u), (unsigned char)((v >> 16) & 255u), (unsigned char)(v >> 24)); };
   r.a = px(q.x); r.c = px(q.y); r.b = px(q.z); r.d = px(q.w);
@@ -308,36 +285,9 @@ __device__ __forceinline__ void tex_fetch_aniso_p2(const CV& cv, const uint8_t* 
   const float du = along_x ? ux : uy, dv = along_x ? vx : vy;
   const bool two = fl > 0.0f && l0 + 1 < nlev;
   const int l1 = two ? l0 + 1 : l0;
-#ifdef HP_TEX_NO_TABLE  // diagnostics: the level geometry / probe positions recomputed per fetch instead of read from the LDS table
-  int off0 = 0, w0 = tw, h0 = th;
-  for (int k = 0; k < l0; ++k) { off0 += 8 * (w0 + 1) * h0; w0 = w0 > 1 ? w0 >> 1 : 1; h0 = h0 > 1 ? h0 >> 1 : 1; }
-  int off1 = off0, w1 = w0, h1 = h0;
-  if (l1 != l0) { off1 += 8 * (w0 + 1) * h0; w1 = w0 > 1 ? w0 >> 1 : 1; h1 = h0 > 1 ? h0 >> 1 : 1; }
-  float tt[16];
-#pragma unroll
-  for (int k = 0; k < 16; ++k) tt[k] = (float)(k + 1) / (float)(N + 1) - 0.5f;
-#else
   const int off0 = mt.qoff[l0], w0 = mt.w[l0], h0 = mt.h[l0];
   const int off1 = mt.qoff[l1], w1 = mt.w[l1], h1 = mt.h[l1];
   const float* const tt = mt.tt[N - 1];
-#endif
-#ifdef HP_TEX_DEBUG_MATH  // diagnostics: colour = a hash of everything the fetch addresses are computed from; no texel is read
-  {
-#if HP_TEX_DEBUG_MATH == 1   // the interpolated coordinates and their derivatives (the records' planes)
-    uint32_t hsh = __float_as_uint(u) * 31u ^ __float_as_uint(v) * 131u ^ __float_as_uint(ux) * 7u ^ __float_as_uint(vx) * 13u ^ __float_as_uint(uy) * 3u ^ __float_as_uint(vy) * 5u;
-#elif HP_TEX_DEBUG_MATH == 2  // the footprint arithmetic on them (sqrt, division, ceil, log2)
-    uint32_t hsh = (uint32_t)N * 2654435761u ^ (uint32_t)l0 * 40503u ^ __float_as_uint(fl);
-#elif HP_TEX_DEBUG_MATH == 3  // the level table
-    uint32_t hsh = (uint32_t)off0 ^ (uint32_t)w0 * 17u ^ (uint32_t)h0 * 257u ^ (uint32_t)off1 * 3u ^ __float_as_uint(tt[0]);
-#else
-    uint32_t hsh = (uint32_t)N * 2654435761u ^ (uint32_t)l0 * 40503u ^ __float_as_uint(fl) ^ __float_as_uint(u) * 31u ^ __float_as_uint(v) * 131u ^
-                   __float_as_uint(du) * 7u ^ __float_as_uint(dv) * 13u ^ (uint32_t)off0 ^ (uint32_t)w0 * 17u;
-#endif
-    hsh ^= hsh >> 15; hsh *= 2246822519u; hsh ^= hsh >> 13;
-    rgb[0] = (float)(hsh & 255u) / 255.0f; rgb[1] = (float)((hsh >> 8) & 255u) / 255.0f; rgb[2] = (float)((hsh >> 16) & 255u) / 255.0f;
-    return;
-  }
-#endif
   float acc[3] = {0.0f, 0.0f, 0.0f};
   for (int i = 1; i <= N; i += 2) {
     const bool second = i + 1 <= N;
@@ -478,14 +428,8 @@ __device__ __forceinline__ bool setup_subtri(const RasterArgs& a, const SnapCorn
     const float uy = (NU.qy - tu * W.qy) * iw * (float)tw, vy = (NV.qy - tv * W.qy) * iw * (float)th;
     const float p2x = ux * ux + vx * vx, p2y = uy * uy + vy * vy;
     const float hi2 = fmaxf(p2x, p2y), lo2 = fminf(p2x, p2y);
-#ifndef HP_CLS_RATIO2
-#define HP_CLS_RATIO2 16.0f
-#endif
-    cls = (hi2 > HP_CLS_RATIO2 * lo2) ? 1u : 0u;  // Pmax / Pmin > 4: more than four probes = more than two rounds of the probe-pair loop
+    cls = (hi2 > 16.0f * lo2) ? 1u : 0u;  // Pmax / Pmin > 4: more than four probes = more than two rounds of the probe-pair loop
   }
-#ifdef HP_SABL_NOREC
-  if (a.w > 0 && fb(W.q0 + NU.q0 + NV.q0) != 0x12345u) { row_lo = ia; row_hi = i1; cols = j1 - ja + 1; return true; }
-#endif
   rec[0] = make_uint4(pk(j0, i0), (big ? 1u : 0u) | (cls << 1), pk(rx[0], ry[0]), pk(rx[1], ry[1]));
   rec[1] = make_uint4(pk(rx[2], ry[2]), fb(W.q0), fb(W.qx), fb(W.qy));
   rec[2] = make_uint4(fb(NU.q0), fb(NU.qx), fb(NU.qy), fb(NV.q0));
@@ -700,16 +644,7 @@ __device__ __forceinline__ void shade_centre(const A& a, const ShadeCtx& cx, int
   const int64_t voff = cx.voff, toff = cx.toff;
   const int tw = cx.tw, th = cx.th, view = cx.view, q8 = cx.q8;
   const uint4* const r = cx.recs + (int64_t)(id & 0x3FFFFFFF) * a.rec_q;  // (bit 30 of a key's low word: the probe-count class)
-#ifdef HP_REC_SCOPE  // diagnostics: the record read word by word with scoped atomic loads (1: agent = L2-served, 2: system = memory-served)
-  auto ldw = [&](int k) {
-    const uint32_t* wp = reinterpret_cast<const uint32_t*>(r) + k;
-    return HP_REC_SCOPE == 2 ? __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM) : __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  };
-  const uint4 r0 = make_uint4(ldw(0), ldw(1), ldw(2), ldw(3)), r1 = make_uint4(ldw(4), ldw(5), ldw(6), ldw(7));
-  const uint4 r2 = make_uint4(ldw(8), ldw(9), ldw(10), ldw(11)), r3 = make_uint4(ldw(12), ldw(13), ldw(14), ldw(15));
-#else
   const uint4 r0 = r[0], r1 = r[1], r2 = r[2], r3 = r[3];
-#endif
   const int ox = (int)(short)(r0.x & 0xFFFFu), oy = (int)r0.x >> 16;
   const PlaneQ W{__uint_as_float(r1.y), __uint_as_float(r1.z), __uint_as_float(r1.w)};
   const float fx = (float)(j - ox) + 0.5f, fy = (float)(i - oy) + 0.5f;
@@ -864,11 +799,7 @@ __device__ __forceinline__ void crop_taps(const float* __restrict__ img, int HW,
       const float wj = fx.w[c2];
 #pragma unroll
       for (int c = 0; c < NC; ++c) {
-#ifdef HP_RABL_CROP_NOLOAD
-        const float v = wj + (float)off;
-#else
         const float v = img[(sc0 + c) * HW + off];
-#endif
         racc[c] += wj * v;
         if (sc0 + c == 3) rv += wj * (v > 0.0f ? 1.0f : 0.0f);
       }
@@ -879,22 +810,6 @@ __device__ __forceinline__ void crop_taps(const float* __restrict__ img, int HW,
     vacc += wi * rv;
   }
 }
-
-#ifdef HP_RASTER_STAMPS
-// -DHP_RASTER_STAMPS (tools/raster_stamps.py): shader cycles between the phases of the band kernel, summed over the workgroups
-// (thread 0's clock), [phase] and workgroup count in [15]
-__device__ unsigned long long hp_rstamp[16];
-#define HP_STAMP(k)                                                                         \
-  do {                                                                                      \
-    if (threadIdx.x == 0) {                                                                 \
-      const unsigned long long now_ = __builtin_readcyclecounter();                          \
-      atomicAdd(&hp_rstamp[k], now_ - stamp_t_);                                            \
-      stamp_t_ = now_;                                                                      \
-    }                                                                                       \
-  } while (0)
-#else
-#define HP_STAMP(k) do { } while (0)
-#endif
 
 // ---- coverage ---------------------------------------------------------------------------------------------------------
 // The three edge functions of a record in the form E_k(X, Y) = A_k X + B_k Y + C_k on sub-pixel coordinates relative to the
@@ -928,10 +843,6 @@ __device__ __forceinline__ bool candidate_range(const A& a, const int (&rx)[3], 
 template <int NS, bool HALF, bool ANISO, bool WIDE>
 __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO) ? 6 : 4) void raster_kernel(RasterArgs a_in, int npix_max) {
   constexpr int kThreads = band_threads(NS, WIDE);
-#ifdef HP_RASTER_STAMPS
-  unsigned long long stamp_t_ = __builtin_readcyclecounter();
-  if (threadIdx.x == 0) atomicAdd(&hp_rstamp[15], 1ull);
-#endif
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   __shared__ int big_q[kBigQueue];
   __shared__ int big_n, n_cov, n_cov_hi, span_max[2];  // n_cov / n_cov_hi: list entries of the two probe-count classes (front / back)
@@ -1002,19 +913,13 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
     if (tid == 0) { big_n = 0; n_cov = 0; n_cov_hi = 0; }
   }
   __syncthreads();
-  HP_STAMP(0);  // head: list / record loads in flight, z-buffer initialised
   if (!band_empty && tid == 0) { a.bin_count[2 * lin] = 0; a.bin_count[2 * lin + 1] = 0; }  // consumed (every thread has read them by now): zero for the next launch
-#ifdef HP_RABL_NO_COVER
-  const int cnt_loop = 0;
-#else
-  const int cnt_loop = cnt;
-#endif
   const float w_near = 1.0f / kZNear, w_far = 1.0f / kZFar;
   // ---- coverage + depth: a lane owns a listed record; the next one's loads are in flight while it walks ----
-  for (int k = tid; k < cnt_loop; k += kThreads) {
+  for (int k = tid; k < cnt; k += kThreads) {
     const int id = id_n;
     const uint4 q0 = q0_n, q1 = q1_n;
-    if (k + kThreads < cnt_loop) {
+    if (k + kThreads < cnt) {
       id_n = entry(k + kThreads);
       q0_n = recs[(int64_t)id_n * a.rec_q]; q1_n = recs[(int64_t)id_n * a.rec_q + 1];
     }
@@ -1071,7 +976,6 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
     }
   }
   if (!band_empty) __syncthreads();
-  HP_STAMP(1);  // coverage walk
   // ---- large footprints and far-reaching corners: the whole workgroup walks the candidate pixels, edge functions in
   // double precision (exact: |A X| < 2^43) ----
   const int nbig = band_empty ? 0 : min(big_n, kBigQueue);
@@ -1121,7 +1025,6 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
     }
   }
   if (!band_empty) __syncthreads();
-  HP_STAMP(2);  // cooperative walk of large footprints
 
   // ---- the object's mip table (LDS), filled while the coverage results settle: its inputs hang on a chain of dependent scalar
   // loads (obj_ids -> obj row) that used to sit in front of the kernel's first barrier ----
@@ -1130,11 +1033,7 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
     int off = 0, qo = 0, lw = tw, lh = th;
     for (int k = 0; k < tid; ++k) { off += 4 * lw * lh; qo += 8 * (lw + 1) * lh; lw = lw > 1 ? lw >> 1 : 1; lh = lh > 1 ? lh >> 1 : 1; }
     mips.off[tid] = off; mips.w[tid] = lw; mips.h[tid] = lh; mips.qoff[tid] = qo;
-#ifdef HP_TEX_NO_QUADS
-    if (tid == 0) mips.p2 = 0;
-#else
     if (tid == 0) mips.p2 = qbase >= 0;
-#endif
   }
   if (ANISO && tid < 256) {
     const int N = (tid >> 4) + 1, i = (tid & 15) + 1;
@@ -1177,14 +1076,8 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
       }
     }
     __syncthreads();
-    HP_STAMP(3);  // compaction (single sample)
     const int ncov_lo = n_cov, ncov = ncov_lo + (ANISO ? n_cov_hi : 0);
-#ifdef HP_RABL_NO_SHADE
-    const int ncov_loop = a.w < 0 ? ncov : 0;
-#else
-    const int ncov_loop = ncov;
-#endif
-    for (int q = tid; q < ncov_loop; q += kThreads) {
+    for (int q = tid; q < ncov; q += kThreads) {
       const int p = L.plist[q < ncov_lo ? q : list_cap - 1 - (q - ncov_lo)];
       const int pr = (int)(((unsigned long long)p * a.w_magic) >> 32);
       const int i = row0 + pr, j = p - pr * a.w;
@@ -1268,14 +1161,8 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
       }
     }
     __syncthreads();
-    HP_STAMP(3);  // compaction of the invocations
     const int ninv_lo = n_cov, ninv = ninv_lo + (ANISO ? n_cov_hi : 0);
-#ifdef HP_RABL_NO_SHADE
-    const int ninv_loop = a.w < 0 ? ninv : 0;
-#else
-    const int ninv_loop = ninv;
-#endif
-    for (int q = tid; q < ninv_loop; q += kThreads) {
+    for (int q = tid; q < ninv; q += kThreads) {
       const unsigned e = L.plist[q < ninv_lo ? q : list_cap - 1 - (q - ninv_lo)];
       const int p = (int)(e & 0x3FFFu), sm = (int)(e >> 14);
       const int pr = (int)(((unsigned long long)p * a.w_magic) >> 32);
@@ -1293,7 +1180,6 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
     }
   }
   __syncthreads();
-  HP_STAMP(4);  // shading
 
   // ---- output pass: pixel-parallel; crop taps + the view's run(s) of the pixel record, or the strided planes ----
   const float zn = a.depth_norm_z ? a.depth_norm_z[item] : 1.0f;
@@ -1321,11 +1207,7 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
     float cropv[4] = {0.f, 0.f, 0.f, 0.f};
     if (a.rec) {
       // ---- crop channels of this pixel (roi_align of the frame; same taps in the same order as crop_tile_kernel) ----
-#ifdef HP_RABL_NO_CROP
-      if (ncrop > 0 && a.w < 0) {
-#else
       if (ncrop > 0) {
-#endif
         const Fold fy = L.fy[pr], fx = L.fx[j];
         float acc[4] = {0.f, 0.f, 0.f, 0.f};
         float vacc = 0.0f;
@@ -1390,9 +1272,6 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
       }
       const int64_t pix = (int64_t)item * a.rec_item + (int64_t)i * a.rec_row + (int64_t)j * a.rec_col;
       const int c0 = a.v_c0[vi], cc0 = a.v_crop_c0[vi];
-#ifdef HP_RABL_NO_STORE
-      if (a.w > 0 && cropv[0] + rend[0] != -123.0f) continue;
-#endif
       if (HALF) {
         _Float16* const o = reinterpret_cast<_Float16*>(a.rec) + pix;
         if (a.rec_own_all) {  // one view owns the whole 16-half record: two 16-B stores, pads included
@@ -1479,7 +1358,6 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
       else a.depth[dof] = d_out;
     }
   }
-  HP_STAMP(6);  // output pass issued
 }
 
 }  // namespace hp
@@ -1795,10 +1673,3 @@ extern "C" int hp_render_inputs(const hp_mesh_store* store, int n_items, int vie
   return launch_raster(store, a, a.n, crop, (hipStream_t)stream);
 }
 
-#ifdef HP_RASTER_STAMPS
-extern "C" int hp_debug_raster_stamps(unsigned long long* out, int reset) {
-  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(hp::hp_rstamp), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-  if (reset) { unsigned long long z[16] = {0}; if (hipMemcpyToSymbol(HIP_SYMBOL(hp::hp_rstamp), z, sizeof(z)) != hipSuccess) return -1; }
-  return 0;
-}
-#endif

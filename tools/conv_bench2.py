@@ -47,14 +47,4 @@ for half in (False, True):
                 ref = torch.relu(ref)
             err = float((y[:nb].float() - ref).abs().max() / ref.abs().max())
             fl = 2.0 * b * h * w * cout * 9 * cin
-            extra = ""
-            try:  # -DHP_PP_STAMPS build: cycles inside conv3x3_pp (all launches since the last read)
-                import ctypes
-                from happypose_amd import _ffi
-                buf = (ctypes.c_double * 8)()
-                if _ffi.lib().hp_debug_pp_stamps(buf) == 0 and buf[3] > 0:
-                    extra = (f"  | {buf[0] / buf[1] * 100:5.0f} MHz {buf[0] / buf[2]:6.0f} cyc/tap {buf[2] / buf[3]:4.0f} taps/item; per item: prologue "
-                             f"{buf[4] / buf[3]:6.0f} K loop {buf[0] / buf[3]:7.0f} epilogue {buf[5] / buf[3]:6.0f} cycles")
-            except AttributeError:
-                pass
-            print(f"{'f16' if half else 'f32'} B={b:4d} {h:3d}x{w:3d} {cin:4d}->{cout:4d} {name:5s} {ms*1e3:8.1f} us {fl/ms/1e9:7.1f} TFLOP/s  rel err {err:.1e}{extra}")
+            print(f"{'f16' if half else 'f32'} B={b:4d} {h:3d}x{w:3d} {cin:4d}->{cout:4d} {name:5s} {ms*1e3:8.1f} us {fl/ms/1e9:7.1f} TFLOP/s  rel err {err:.1e}")

@@ -1,4 +1,4 @@
-"""Rasteriser / crop stage timing on the C2 inputs (bench.stage_rates) -- used with HAPPYPOSE_AMD_LIB pointing at ablation builds."""
+"""Rasteriser / crop stage timing on the C2 inputs (bench.stage_rates) -- run with HAPPYPOSE_AMD_LIB pointing at an A/B library (HP_BUILD_VARIANT, happypose_amd/build.py)."""
 import json, sys, os
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np, torch

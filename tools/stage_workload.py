@@ -1,5 +1,5 @@
 """Rasteriser + crop on the C2 and C3 inputs in the product layout, a few repetitions each: the command the rocprofv3
-PMC passes of profiles/r03_raster_* run (tools/profile_r03.sh).  Prints the event-timed durations and the ALGORITHMIC
+PMC passes of profiles/r03_raster_* ran.  Prints the event-timed durations and the ALGORITHMIC
 bytes per call as JSON so that counter bytes / algorithmic bytes can be stated."""
 import json
 import os

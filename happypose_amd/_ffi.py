@@ -75,6 +75,8 @@ _PROTOS = {
     "hp_net_create": (C.c_void_p, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "hp_net_destroy": (None, [C.c_void_p]),
     "hp_net_add_conv": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p] + [C.c_int] * 11),
+    "hp_net_add_dwconv": (C.c_int, [C.c_void_p, C.c_char_p, C.c_char_p] + [C.c_int] * 10),
+    "hp_net_add_se": (C.c_int, [C.c_void_p, C.c_char_p] + [C.c_int] * 5),
     "hp_net_add_output": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int]),
     "hp_net_input_channels_padded": (C.c_int, [C.c_void_p]),
     "hp_net_set_param": (C.c_int, [C.c_void_p, C.c_char_p, c_f32p, C.c_int64]),

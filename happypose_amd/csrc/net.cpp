@@ -183,6 +183,27 @@ void want(Net& n, int slot, size_t floats) {
   if (n.buf_floats_per_sample[slot] < floats) n.buf_floats_per_sample[slot] = floats;
 }
 
+// the two memory-bound ops of an MBConv block (EfficientNet plan; caller-described graphs: hp_net_add_dwconv / hp_net_add_se)
+void add_dw(Net& n, const std::string& wname, const std::string& bn, int C, int k, int stride, int pad, int H, int W, int Ho, int Wo,
+            int in_buf, int out_buf) {
+  auto D = std::make_unique<DwLayer>();
+  D->wname = wname; D->bn = bn;
+  D->C = C; D->k = k; D->stride = stride; D->pad = pad; D->H = H; D->W = W; D->Ho = Ho; D->Wo = Wo;
+  D->in_buf = in_buf; D->out_buf = out_buf;
+  n.flops_per_sample += 2.0 * Ho * Wo * C * k * k;
+  Op od; od.kind = OP_DW; od.conv = (int)n.dws.size();
+  n.dws.push_back(std::move(D)); n.ops.push_back(od);
+}
+
+void add_se(Net& n, const std::string& prefix, int C, int Cse, int HW, int in_buf) {
+  auto S = std::make_unique<SeLayer>();
+  S->prefix = prefix; S->C = C; S->Cse = Cse; S->HW = HW; S->in_buf = in_buf;
+  n.se_max_c = std::max(n.se_max_c, C);
+  n.flops_per_sample += 2.0 * 2.0 * C * Cse;
+  Op os; os.kind = OP_SE; os.conv = (int)n.ses.size();
+  n.ses.push_back(std::move(S)); n.ops.push_back(os);
+}
+
 // Build the op list.  Arena slots: 0 = stem output, then a rotating set of 4.
 int build_graph(Net& n) {
   n.convs.clear(); n.ops.clear(); n.buf_floats_per_sample.clear(); n.flops_per_sample = 0.0;
@@ -297,20 +318,9 @@ int build_graph_efficientnet(Net& n) {
       }
       eff_same_pad(k, stride, &lo, &tot);
       const int Ho = (H + tot - k) / stride + 1, Wo = (W + tot - k) / stride + 1;
-      auto D = std::make_unique<DwLayer>();
-      D->wname = p + "._depthwise_conv.weight"; D->bn = p + "._bn1";
-      D->C = mid; D->k = k; D->stride = stride; D->pad = lo; D->H = H; D->W = W; D->Ho = Ho; D->Wo = Wo;
-      D->in_buf = src; D->out_buf = 3;
+      add_dw(n, p + "._depthwise_conv.weight", p + "._bn1", mid, k, stride, lo, H, W, Ho, Wo, src, 3);
       want(n, 3, (size_t)Ho * Wo * mid);
-      n.flops_per_sample += 2.0 * Ho * Wo * mid * k * k;
-      Op od; od.kind = OP_DW; od.conv = (int)n.dws.size();
-      n.dws.push_back(std::move(D)); n.ops.push_back(od);
-      auto S = std::make_unique<SeLayer>();
-      S->prefix = p; S->C = mid; S->Cse = cse; S->HW = Ho * Wo; S->in_buf = 3;
-      n.se_max_c = std::max(n.se_max_c, mid);
-      n.flops_per_sample += 2.0 * 2.0 * mid * cse;
-      Op os; os.kind = OP_SE; os.conv = (int)n.ses.size();
-      n.ses.push_back(std::move(S)); n.ops.push_back(os);
+      add_se(n, p, mid, cse, Ho * Wo, 3);
       const bool skip = stride == 1 && cin == out_f;
       const int dst = 1 - cur;
       const int c = add_conv(n, p + "._project_conv.weight", p + "._bn2", "", mid, out_f, 1, 1, 0, HP_ACT_NONE, Ho, Wo, 3, dst,
@@ -640,7 +650,12 @@ extern "C" int hp_net_add_conv(hp_net* net, const char* weight_name, const char*
   HP_REQUIRE(net && net->arch == HP_ARCH_CUSTOM && !net->finalized, "hp_net_add_conv: needs an unfinalized HP_ARCH_CUSTOM network");
   HP_REQUIRE(weight_name && cin >= 1 && cout >= 1 && k >= 1 && (stride == 1 || stride == 2) && pad >= 0 && H >= 1 && W >= 1,
              "hp_net_add_conv: bad layer geometry");
-  HP_REQUIRE(act >= HP_ACT_NONE && act <= HP_ACT_RELU, "hp_net_add_conv: activation must be none or ReLU");
+  const bool gated = (act & HP_CONV_GATED) != 0;  // the input is multiplied by the gate of the squeeze-excitation op before it
+  act &= ~HP_CONV_GATED;
+  HP_REQUIRE(act >= HP_ACT_NONE && act <= HP_ACT_SWISH, "hp_net_add_conv: activation must be none, ReLU or swish");
+  HP_REQUIRE(!gated || (k == 1 && cin % 4 == 0 && in_slot >= 0 && !net->ses.empty() && net->ses.back()->C == cin &&
+                        net->ses.back()->in_buf == in_slot),
+             "hp_net_add_conv: a gated layer is a 1x1 convolution on the slot the last hp_net_add_se pooled (cin % 4 == 0)");
   HP_REQUIRE(in_slot >= -1 && in_slot < 32 && out_slot >= 0 && out_slot < 32 && res_slot >= -1 && res_slot < 32 && out_slot != in_slot &&
                  out_slot != res_slot, "hp_net_add_conv: bad arena slots");
   HP_REQUIRE(in_slot >= 0 || (cin == net->n_inputs && H == net->h && W == net->w), "hp_net_add_conv: the first layer must match the network input");
@@ -650,7 +665,41 @@ extern "C" int hp_net_add_conv(hp_net* net, const char* weight_name, const char*
   ConvLayer& L = *net->convs[c];
   if (cout4 != cout) L.cout_real = cout;
   if (bias_name && bias_name[0]) L.bias_name = bias_name;
+  if (gated) L.se = 1;
   want(*net, out_slot, (size_t)L.Ho * L.Wo * cout4);
+  return HP_OK;
+}
+
+// The MBConv ops of build_graph_efficientnet for a caller-described graph: forward_chunk picks their launches (fused front,
+// strip pooling, se_pool_kernel) as it does for the EfficientNet plan.
+extern "C" int hp_net_add_dwconv(hp_net* net, const char* weight_name, const char* bn_prefix, int C, int k, int stride, int pad,
+                                 int H, int W, int Ho, int Wo, int in_slot, int out_slot) {
+  HP_REQUIRE(net && net->arch == HP_ARCH_CUSTOM && !net->finalized, "hp_net_add_dwconv: needs an unfinalized HP_ARCH_CUSTOM network");
+  HP_REQUIRE(weight_name && bn_prefix && C >= 4 && C % 4 == 0 && (k == 3 || k == 5) && (stride == 1 || stride == 2) && pad >= 0 &&
+                 pad < k && H >= 1 && W >= 1 && Ho >= 1 && Wo >= 1, "hp_net_add_dwconv: bad layer geometry");
+  // the bottom / right padding the explicit output size implies: 0 .. k - 1 rows, like the top / left one
+  const int hi_h = (Ho - 1) * stride + k - pad - H, hi_w = (Wo - 1) * stride + k - pad - W;
+  HP_REQUIRE(hi_h >= 0 && hi_h < k && hi_w >= 0 && hi_w < k, "hp_net_add_dwconv: output size does not fit the input and the padding");
+  HP_REQUIRE((int64_t)H * W * C * 4 < (int64_t)1 << 31 && (int64_t)Ho * Wo * C * 4 < (int64_t)1 << 31,
+             "hp_net_add_dwconv: a map of one image exceeds the kernels' 32-bit offsets");
+  HP_REQUIRE(in_slot >= -1 && in_slot < 32 && out_slot >= 0 && out_slot < 32 && out_slot != in_slot, "hp_net_add_dwconv: bad arena slots");
+  if (in_slot < 0)
+    HP_REQUIRE(C == net->c_pad && C == net->n_inputs && H == net->h && W == net->w, "hp_net_add_dwconv: the first layer must match the network input");
+  else
+    HP_REQUIRE(in_slot < (int)net->buf_floats_per_sample.size() && (size_t)H * W * C <= net->buf_floats_per_sample[in_slot],
+               "hp_net_add_dwconv: the input slot is unwritten or smaller than the input map");
+  net->bn_eps = 1e-3f;  // the BatchNorm of an MBConv block is EfficientNet's (hp_net_add_conv layers take no BatchNorm)
+  add_dw(*net, weight_name, bn_prefix, C, k, stride, pad, H, W, Ho, Wo, in_slot, out_slot);
+  want(*net, out_slot, (size_t)Ho * Wo * C);
+  return HP_OK;
+}
+
+extern "C" int hp_net_add_se(hp_net* net, const char* prefix, int C, int Cse, int H, int W, int in_slot) {
+  HP_REQUIRE(net && net->arch == HP_ARCH_CUSTOM && !net->finalized, "hp_net_add_se: needs an unfinalized HP_ARCH_CUSTOM network");
+  HP_REQUIRE(prefix && C >= 4 && C % 4 == 0 && Cse >= 1 && Cse <= 128 && H >= 1 && W >= 1, "hp_net_add_se: bad layer geometry");
+  HP_REQUIRE(in_slot >= 0 && in_slot < (int)net->buf_floats_per_sample.size() && (size_t)H * W * C <= net->buf_floats_per_sample[in_slot],
+             "hp_net_add_se: the input slot is unwritten or smaller than the input map");
+  add_se(*net, prefix, C, Cse, H * W, in_slot);
   return HP_OK;
 }
 
@@ -948,7 +997,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       if (oi + 2 < net->ops.size() && net->ops[oi + 1].kind == OP_DW && net->ops[oi + 2].kind == OP_SE && L.w_isplit.p && L.kh == 1 &&
           L.relu == HP_ACT_SWISH && !L.se && L.res_buf < 0 && !a.pre_scale && conv_use_split(algo, L.H, L.W, L.cin, L.cout)) {
         const DwLayer& D = *net->dws[net->ops[oi + 1].conv];
-        if (D.in_buf == L.out_buf && D.C == L.cout && net->ses[net->ops[oi + 2].conv]->in_buf == D.out_buf &&
+        if (D.in_buf == L.out_buf && D.C == L.cout && D.H == L.Ho && D.W == L.Wo && a.bias && net->ses[net->ops[oi + 2].conv]->in_buf == D.out_buf &&
             mbconv_front_applicable(L.cin, L.Kpad, L.cout, D.k, D.stride))
           fdw = &D;
       }
@@ -1039,7 +1088,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       const DwLayer& D = *net->dws[op.conv];
       buf_amax[D.out_buf] = -1;  // the depthwise kernels do not track their range
       DwArgs d{};
-      d.x = (const float*)net->bufs[D.in_buf].p; d.w = (const float*)D.w.p; d.bias = (const float*)D.bias.p;
+      d.x = D.in_buf < 0 ? d_x : (const float*)net->bufs[D.in_buf].p; d.w = (const float*)D.w.p; d.bias = (const float*)D.bias.p;
       d.y = (float*)net->bufs[D.out_buf].p;
       d.n = batch; d.H = D.H; d.W = D.W; d.C = D.C; d.Ho = D.Ho; d.Wo = D.Wo; d.k = D.k; d.stride = D.stride;
       d.pad_t = d.pad_l = D.pad;

@@ -634,7 +634,11 @@ class GraphNet(Net):
     """``HP_ARCH_CUSTOM``: a feed-forward graph of convolutions described layer by layer (the detector's RoI heads).
     ``layers``: dicts ``weight, bias, cin, cout, k, stride, pad, relu, H, W, src, dst, res`` in execution order
     (``src = -1`` = the network input, arena slots 0..31); ``outputs``: ``(slot, H, W, C)`` read back by
-    :meth:`Net.feature_maps` (``C`` rounded up to 4)."""
+    :meth:`Net.feature_maps` (``C`` rounded up to 4).  A layer's ``kind`` (default ``"conv"``) may also name the ops of an
+    EfficientNet MBConv block (block-level tests; the launches are the ones the EfficientNet plan picks):
+    ``"dw"``: ``weight, bn, C, k, stride, pad`` (top / left), ``H, W, Ho, Wo, src, dst`` (``hp_net_add_dwconv``);
+    ``"se"``: ``prefix, C, Cse, H, W, src`` (``hp_net_add_se``); a conv layer with ``relu=2`` is activated by swish, one with
+    ``gated=True`` takes the gate of the ``"se"`` layer before it on its input (the 1x1 projection)."""
 
     def __init__(self, c_in: int, h: int, w: int, layers, outputs, state_dict, max_batch: int, device="cuda"):
         self.device = torch.device(device)
@@ -645,8 +649,20 @@ class GraphNet(Net):
             if not self._h:
                 raise _ffi.HipLibraryError("hp_net_create: " + lib().hp_last_error().decode())
             for L in layers:
+                kind = L.get("kind", "conv")
+                if kind == "dw":
+                    check(lib().hp_net_add_dwconv(self.handle, L["weight"].encode(), L["bn"].encode(), L["C"], L["k"], L.get("stride", 1),
+                                                  L["pad"], L["H"], L["W"], L["Ho"], L["Wo"], L["src"], L["dst"]),
+                          f"hp_net_add_dwconv({L['weight']})")
+                    continue
+                if kind == "se":
+                    check(lib().hp_net_add_se(self.handle, L["prefix"].encode(), L["C"], L["Cse"], L["H"], L["W"], L["src"]),
+                          f"hp_net_add_se({L['prefix']})")
+                    continue
+                assert kind == "conv", kind
+                act = int(L.get("relu", False)) | (CONV_GATED if L.get("gated") else 0)
                 check(lib().hp_net_add_conv(self.handle, L["weight"].encode(), (L.get("bias") or "").encode(), L["cin"], L["cout"], L["k"],
-                                            L.get("stride", 1), L.get("pad", 0), int(L.get("relu", False)), L["H"], L["W"], L["src"],
+                                            L.get("stride", 1), L.get("pad", 0), act, L["H"], L["W"], L["src"],
                                             L["dst"], L.get("res", -1)), f"hp_net_add_conv({L['weight']})")
             for slot, oh, ow, oc in outputs:
                 check(lib().hp_net_add_output(self.handle, slot, oh, ow, (oc + 3) // 4 * 4), "hp_net_add_output")
@@ -672,6 +688,7 @@ class GraphNet(Net):
 
 
 STATUS_NONFINITE, STATUS_EXACT_ONLY = 1, 2
+CONV_GATED = 0x100  # HP_CONV_GATED
 
 
 def profile_mark_reference(device) -> None:

@@ -338,8 +338,19 @@ int hp_tco_init_autodepth(const hp_mesh_store* store, int n, const float* d_boxe
  * c_in, h, w), then hp_net_add_conv per layer in execution order (arena slots 0..31; in_slot -1 = the network input;
  * weight [cout][cin][k][k] and optional bias [cout] by parameter name; act 0 none / 1 ReLU; res_slot >= 0 adds that slot
  * before the activation), hp_net_add_output for every slot to read back, hp_net_set_param, hp_net_finalize, hp_net_forward
- * (heads NULL), hp_net_copy_feature_map.  Output channel counts are rounded up to 4 (zero rows). */
+ * (heads NULL), hp_net_copy_feature_map.  Output channel counts are rounded up to 4 (zero rows).
+ * The graph may also hold the ops of an EfficientNet MBConv block, or any prefix of one, which then run through the launches
+ * the HP_ARCH_EFFICIENTNET_B3 plan picks for them (block-level tests):
+ *   hp_net_add_conv with act 2 (swish): the 1x1 expansion; with HP_CONV_GATED or-ed into act: the 1x1 projection, whose input
+ *     is multiplied by the gate of the hp_net_add_se before it (same slot, cin = its C);
+ *   hp_net_add_dwconv: depthwise k x k (k 3 or 5, stride 1 or 2) + BatchNorm (eps 1e-3, folded) + swish on C % 4 == 0
+ *     channels; weight [C][1][k][k] and the BatchNorm prefix ("<prefix>.weight / .bias / .running_mean / .running_var") by
+ *     parameter name; pad = top / left padding, the bottom / right one follows from the explicit output size (Ho, Wo): the
+ *     "same" padding of EfficientNet is asymmetric;
+ *   hp_net_add_se: squeeze-excitation vector of slot in_slot [n][H][W][C]: mean over H x W -> "<prefix>._se_reduce" [Cse][C]
+ *     + bias -> swish -> "<prefix>._se_expand" [C][Cse] + bias -> sigmoid (Cse <= 128). */
 #define HP_ARCH_CUSTOM 5
+#define HP_CONV_GATED 0x100
 
 typedef struct hp_net hp_net;
 
@@ -347,6 +358,9 @@ hp_net* hp_net_create(int arch, int n_inputs, int h, int w);
 void hp_net_destroy(hp_net* net);
 int hp_net_add_conv(hp_net* net, const char* weight_name, const char* bias_name, int cin, int cout, int k, int stride, int pad,
                     int act, int H, int W, int in_slot, int out_slot, int res_slot);
+int hp_net_add_dwconv(hp_net* net, const char* weight_name, const char* bn_prefix, int C, int k, int stride, int pad, int H, int W,
+                      int Ho, int Wo, int in_slot, int out_slot);
+int hp_net_add_se(hp_net* net, const char* prefix, int C, int Cse, int H, int W, int in_slot);
 int hp_net_add_output(hp_net* net, int slot, int H, int W, int C);
 int hp_net_input_channels_padded(const hp_net* net);
 int hp_net_set_param(hp_net* net, const char* name, const float* h_data, int64_t numel);

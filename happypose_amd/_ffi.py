@@ -33,6 +33,13 @@ class InputLayout(C.Structure):
     _fields_ = [("view_c0", C.c_int * 8), ("crop_c0", C.c_int * 8), ("crop_src0", C.c_int * 8), ("crop_n", C.c_int * 8)]
 
 
+class OpInfo(C.Structure):
+    """``hp_op_info``: one op of a finalized network (``hp_net_op_info``)."""
+
+    _fields_ = [(n, C.c_int) for n in ("kind", "k", "stride", "pad", "act", "H", "W", "Cin", "Ho", "Wo", "Cout", "prologue", "in_slot",
+                                       "res_slot", "out_slot", "elem_bytes", "path", "materialised")] + [("name", C.c_char * 128)]
+
+
 class HipLibraryError(RuntimeError):
     pass
 
@@ -93,6 +100,9 @@ _PROTOS = {
     "hp_net_feature_map": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_void_p), C.POINTER(C.c_int), C.POINTER(C.c_int),
                                      C.POINTER(C.c_int)]),
     "hp_net_copy_feature_map": (C.c_int, [C.c_void_p, C.c_int, C.c_int, c_f32p, C.c_void_p]),
+    "hp_net_n_ops": (C.c_int, [C.c_void_p]),
+    "hp_net_op_info": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(OpInfo)]),
+    "hp_net_set_taps": (C.c_int, [C.c_void_p, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_void_p)]),
     "hp_detector_preprocess": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_float), C.POINTER(C.c_float), c_f32p,
                                          C.c_void_p]),
     "hp_detector_preprocess_resize": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,

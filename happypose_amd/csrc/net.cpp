@@ -123,6 +123,10 @@ struct Net {
   bool exact_only = false;       // sticky after the guard fired: exact-fp32 kernels only
   // dynamic range of the split-fp16 kernels (ConvArgs::amax_in / amax_out): one word per op, zeroed at the start of a forward
   DevBuf amax;
+  // layer-level tests (hp_net_set_taps / hp_net_op_info): per op, where to copy its output and what the last forward launched
+  std::vector<void*> taps;       // empty = no taps; else one entry per op (nullptr = not tapped)
+  std::vector<int> op_path;      // HP_PATH_* per op
+  std::vector<char> op_mat;      // the op's output map was written
   ~Net() { if (h_status) (void)hipHostFree(h_status); }
 };
 
@@ -811,6 +815,9 @@ extern "C" int hp_net_finalize(hp_net* net, int max_batch) {
   }
   { int rc_a = net->amax.alloc((net->ops.size() + 1) * (size_t)kAmaxSlots * kAmaxStride * sizeof(unsigned)); if (rc_a) return rc_a; }
   net->max_batch = max_batch;
+  net->taps.clear();
+  net->op_path.assign(net->ops.size(), HP_PATH_NONE);
+  net->op_mat.assign(net->ops.size(), 0);
   net->params.clear();  // host copies are no longer needed
   net->finalized = true;
   return HP_OK;
@@ -844,8 +851,9 @@ static int ensure_wino_weights(hp_net* net, int algo, hipStream_t stream) {
   return HP_OK;
 }
 
-// d_x: fp32 input [batch][h][w][c_pad]; or (fp16 plan only) d_x16: fp16 input [batch][h][w][cin16 of the stem]
-static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int batch, float* d_pose, float* d_logits,
+// d_x: fp32 input [batch][h][w][c_pad]; or (fp16 plan only) d_x16: fp16 input [batch][h][w][cin16 of the stem];
+// b0 = index of the chunk's first sample in the caller's batch (tap offsets; b0 == 0 starts the launch-path record)
+static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b0, int batch, float* d_pose, float* d_logits,
                          float* d_features, hipStream_t stream) {
   int rc;
   const bool f16 = net->precision == HP_PRECISION_F16;
@@ -912,8 +920,28 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
     t.M = (int64_t)batch * A.Ho * A.Wo;
     return conv_use_split(net_algo, A.H, A.W, A.cin, A.cout) && conv_split_launchable(t) && conv_pp_s2_applicable(t, 3, 3);
   };
+  // host-side record of what this forward launched for op i (hp_net_op_info); a later chunk that differs marks it MIXED
+  auto note = [&](size_t i, int path, bool materialised = true) {
+    if (b0 == 0) { net->op_path[i] = path; net->op_mat[i] = materialised; return; }
+    if (net->op_path[i] != path) net->op_path[i] = HP_PATH_MIXED;
+    net->op_mat[i] = net->op_mat[i] && materialised;
+  };
+  const size_t elem = f16 ? 2 : 4;
+  auto tap = [&](size_t i, bool materialised) -> int {  // copy op i's output map of this chunk to its tap
+    void* dst = net->taps[i];
+    if (!dst || !materialised) return HP_OK;
+    const Op& o = net->ops[i];
+    int slot = o.out_buf;
+    size_t per_sample = (size_t)o.Ho * o.Wo * o.C;
+    if (o.kind == OP_CONV) { const ConvLayer& L = *net->convs[o.conv]; slot = L.out_buf; per_sample = (size_t)L.Ho * L.Wo * L.cout; }
+    else if (o.kind == OP_DW) { const DwLayer& D = *net->dws[o.conv]; slot = D.out_buf; per_sample = (size_t)D.Ho * D.Wo * D.C; }
+    HP_CHECK_HIP(hipMemcpyAsync((char*)dst + (size_t)b0 * per_sample * elem, net->bufs[slot].p, (size_t)batch * per_sample * elem,
+                                hipMemcpyDeviceToDevice, stream));
+    return HP_OK;
+  };
   for (size_t oi = 0; oi < net->ops.size(); ++oi) {
     const Op& op = net->ops[oi];
+    bool written = true;  // this op's output map exists after its turn
     if (sync_ops) {
       HP_CHECK_HIP(hipDeviceSynchronize());
       std::fprintf(stderr, "[hp net] op %d kind %d conv %d (everything before it has completed)\n", op_index, (int)op.kind, op.conv);
@@ -947,15 +975,18 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
         s7.M = a.M; s7.H = L.H; s7.W = L.W; s7.Cin = L.cin16; s7.Ho = L.Ho; s7.Wo = L.Wo; s7.Cout = L.cout; s7.relu = L.relu;
         s7.Kpad = L.cin_real;  // selects the kernel the weights were packed for
         if ((rc = launch_conv_stem7_pool(s7, 1, stream))) return rc;
-        pool_fused = true;
+        pool_fused = true; written = false;
+        note(oi, HP_PATH_STEM7_POOL_F16, false);
         prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, 2.0 * (double)a.M * (256.0 / 192.0) * L.cout * 7 * conv_stem7_f16_krow(L.cin_real));
       } else {
         if ((rc = launch_conv_f16(a, stream))) return rc;
+        note(oi, HP_PATH_CONV_F16);
         prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, 2.0 * (double)((a.M + 127) / 128 * 128) * L.cout * L.Kpad16);
       }
       if ((rc = prof_end(false))) return rc;
     } else if (op.kind == OP_CONV && (int)oi == sc_done) {
       sc_done = -1;  // this shortcut rode in the previous op's launch
+      note(oi, HP_PATH_RODE);
     } else if (op.kind == OP_CONV) {
       ConvLayer& L = *net->convs[op.conv];
       ConvArgs a{};
@@ -1008,7 +1039,8 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
         f.n = batch; f.H = L.H; f.W = L.W; f.Cin = L.cin; f.Cexp = L.cout; f.Ho = fdw->Ho; f.Wo = fdw->Wo; f.k = fdw->k;
         f.stride = fdw->stride; f.pad_t = f.pad_l = fdw->pad; f.Kpad = L.Kpad; f.rows_pad = L.cout_pad;
         rc = launch_mbconv_front(f, stream);
-        front_fused = true; tracks_amax = false;
+        front_fused = true; tracks_amax = false; written = false;
+        note(oi, HP_PATH_MBCONV_FRONT, false);
         buf_amax[fdw->out_buf] = -1;
         dw_partials = mbconv_front_tiles(fdw->Ho, fdw->Wo, fdw->stride);
         const int th = fdw->stride == 1 ? 8 : 4, tw = fdw->stride == 1 ? 16 : 8;
@@ -1022,7 +1054,8 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
         a.y = (float*)net->bufs[next7->out_buf].p;
         a.status = net->d_status;
         rc = launch_conv_stem7_pool(a, 0, stream);
-        pool_fused = true; tracks_amax = false;
+        pool_fused = true; tracks_amax = false; written = false;
+        note(oi, HP_PATH_STEM7_POOL, false);
         const int sc = L.cin % 8 == 0 ? 8 : 4, ks = (7 * sc + 15) / 16;
         mfma_flops = 3.0 / 16.0 * 2.0 * (double)a.M * (256.0 / 192.0) * L.cout * (L.cin / sc) * 7.0 * ks * 16.0;
       } else if (conv_use_split(algo, L.H, L.W, L.cin, L.cout) && L.w_split.p && conv_split_launchable(a)) {
@@ -1039,6 +1072,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
           prof_add(2.0 * (double)a.M * S.cout * S.cin_real, 3.0 * 2.0 * (double)((a.M + 255) / 256 * 256) * S.cout * S.cin / 16.0);
         }
         rc = launch_conv_split(a, stream);
+        note(oi, sc_op >= 0 ? HP_PATH_SPLIT3X3_SHORTCUT : HP_PATH_SPLIT3X3);
         // three fp16 MFMAs per product over whole 256- / 512-row tiles; an fp16 MFMA FLOP occupies the matrix pipe for
         // 1/16 of an fp32 one, so it is counted as 1/16: mfma_flops / time / fp32 peak stays "how busy is the pipe"
         const int64_t bm = (L.cout % 128 == 0 || (L.stride == 1 && conv_pp_split_applicable(a, L.kh, L.kw))) ? 256 : 512;  // 256-row tiles on the ping-pong kernel
@@ -1046,6 +1080,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       } else if (wino_ok && L.w_wino.p && conv_wino_launchable(a)) {
         a.w = (const float*)L.w_wino.p;
         rc = launch_conv_wino(a, stream);
+        note(oi, HP_PATH_WINOGRAD);
         tracks_amax = false;
         mfma_flops = 2.0 * 16.0 * (double)batch * ((L.Ho + 1) / 2) * ((L.Wo + 1) / 2) * L.cin * L.cout;
       } else {
@@ -1061,19 +1096,26 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
             a.y = (float*)net->bufs[next->out_buf].p;
             if (conv_stem_split_applicable(a, L.kh, L.kw, L.run_mode)) {
               rc = launch_conv_stem_split_pool(a, stream);
+              note(oi, HP_PATH_STEM_SPLIT_POOL, false);
               mfma_flops *= 256.0 / 192.0;  // 256 GEMM rows per 6 x 32 conv pixels (7 x 33 computed, the rest padding)
             } else {
               rc = launch_conv_igemm_split_pool(a, stream);
+              note(oi, HP_PATH_IGEMM_SPLIT_POOL, false);
               mfma_flops *= 1.24;  // conv pixels under the tile borders are computed twice (7 x 17 per 6 x 16)
             }
-            pool_fused = true; tracks_amax = false;
+            pool_fused = true; tracks_amax = false; written = false;
           } else {
             rc = launch_conv_igemm_split(a, variant, stream);
+            note(oi, HP_PATH_IGEMM_SPLIT);
           }
           mfma_flops *= 3.0 / 16.0;  // three fp16 MFMAs per product, 1/16 of the pipe time each
-        } else if (algo != HP_CONV_ALGO_IGEMM && a.relu != HP_ACT_SWISH && !L.se && conv_patch_applicable(a, L.kh, L.kw))
+        } else if (algo != HP_CONV_ALGO_IGEMM && a.relu != HP_ACT_SWISH && !L.se && conv_patch_applicable(a, L.kh, L.kw)) {
           rc = launch_conv_patch(a, variant, stream);
-        else rc = launch_conv(a, variant, stream);
+          note(oi, HP_PATH_PATCH);
+        } else {
+          rc = launch_conv(a, variant, stream);
+          note(oi, HP_PATH_GENERIC);
+        }
       }
       if (rc) return rc;
       if (L.out_buf >= 0) buf_amax[L.out_buf] = tracks_amax ? (int)oi : -1;
@@ -1082,6 +1124,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       if ((rc = prof_end(false))) return rc;
     } else if (op.kind == OP_DW && front_fused) {
       front_fused = false;  // the expansion's launch wrote this depthwise output (and the pooling partials) already
+      note(oi, HP_PATH_FUSED_AWAY);
       if ((rc = prof_end(true))) return rc;
     } else if (op.kind == OP_DW) {
       if ((rc = prof_end(true))) return rc;
@@ -1100,6 +1143,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
         dw_partials = dwconv_pool_strips(D.Ho, D.k, D.stride);
       }
       if ((rc = launch_dwconv(d, stream))) return rc;
+      note(oi, HP_PATH_DWCONV);
     } else if (op.kind == OP_SE) {
       if ((rc = prof_end(true))) return rc;
       const SeLayer& S = *net->ses[op.conv];
@@ -1108,30 +1152,32 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
                           (const float*)S.w1.p, (const float*)S.b1.p, (const float*)S.w2.p, (const float*)S.b2.p, batch, S.HW,
                           S.C, S.Cse, dw_partials, stream)))
         return rc;
-      dw_partials = 0;
+      dw_partials = 0; written = false;
+      note(oi, HP_PATH_SE, false);
     } else if (op.kind == OP_RESIZE) {
       buf_amax[op.out_buf] = -1;
       if ((rc = prof_end(true))) return rc;
       if ((rc = launch_resize_nearest((const float*)net->bufs[op.in_buf].p, (float*)net->bufs[op.out_buf].p, batch, op.H, op.W,
                                       op.C, op.Ho, op.Wo, op.conv, stream)))
         return rc;
+      note(oi, HP_PATH_RESIZE);
     } else if (op.kind == OP_MAXPOOL && pool_fused) {
       pool_fused = false;
+      note(oi, HP_PATH_FUSED_AWAY);
       if ((rc = prof_end(true))) return rc;
     } else if (op.kind == OP_MAXPOOL && f16) {
       if ((rc = prof_end(true))) return rc;
       if ((rc = launch_maxpool_f16(net->bufs[op.in_buf].p, net->bufs[op.out_buf].p, batch, op.H, op.W, op.C, op.Ho,
                                    op.Wo, stream)))
         return rc;
-    } else if (op.kind == OP_MAXPOOL && pool_fused) {
-      pool_fused = false;
-      if ((rc = prof_end(true))) return rc;
+      note(oi, HP_PATH_MAXPOOL_F16);
     } else if (op.kind == OP_MAXPOOL) {
       if ((rc = prof_end(true))) return rc;
       buf_amax[op.out_buf] = buf_amax[op.in_buf];  // a max over windows cannot exceed the input's largest magnitude
       if ((rc = launch_maxpool((const float*)net->bufs[op.in_buf].p, (float*)net->bufs[op.out_buf].p, batch,
                                op.H, op.W, op.C, op.Ho, op.Wo, stream)))
         return rc;
+      note(oi, HP_PATH_MAXPOOL);
     } else {
       if ((rc = prof_end(true))) return rc;
       HeadArgs h{};
@@ -1144,9 +1190,21 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       h.pose_out = d_pose; h.logit_out = d_logits; h.features = d_features;
       h.ws_pool = (float*)net->head_ws.p; h.ws_fc = h.ws_pool ? h.ws_pool + (size_t)net->max_batch * 512 : nullptr;
       if ((rc = launch_head(h, batch, stream))) return rc;
+      written = false;
+      note(oi, HP_PATH_HEAD, false);
     }
+    if (!net->taps.empty() && (rc = tap(oi, written))) return rc;
   }
   return prof_end(true);
+}
+
+// taps copy into caller-owned memory at addresses that belong to one forward: not while `stream` captures
+static int taps_allowed(hp_net* net, hipStream_t stream) {
+  if (net->taps.empty()) return HP_OK;
+  hipStreamCaptureStatus st = hipStreamCaptureStatusNone;
+  HP_CHECK_HIP(hipStreamIsCapturing(stream, &st));
+  if (st != hipStreamCaptureStatusNone) return fail(HP_ERR_ARG, "hp_net_forward: taps are set (hp_net_set_taps) and the stream is capturing");
+  return HP_OK;
 }
 
 extern "C" int hp_net_forward(hp_net* net, const float* d_x, int batch, float* d_pose, float* d_logits,
@@ -1160,10 +1218,12 @@ extern "C" int hp_net_forward(hp_net* net, const float* d_x, int batch, float* d
   HP_REQUIRE(net->feature_maps.empty() || (batch <= net->max_batch && !d_pose && !d_logits && !d_features),
              "hp_net_forward: a feature-pyramid network takes at most max_batch images and has no heads (hp_net_feature_map)");
   hipStream_t st = (hipStream_t)stream;
+  int rc_t = taps_allowed(net, st);
+  if (rc_t) return rc_t;
   const size_t in_stride = (size_t)net->h * net->w * net->c_pad;
   for (int b0 = 0; b0 < batch; b0 += net->max_batch) {
     const int nb = batch - b0 < net->max_batch ? batch - b0 : net->max_batch;
-    int rc = forward_chunk(net, d_x + (size_t)b0 * in_stride, nullptr, nb,
+    int rc = forward_chunk(net, d_x + (size_t)b0 * in_stride, nullptr, b0, nb,
                            d_pose ? d_pose + (size_t)b0 * net->pose_dim : nullptr,
                            d_logits ? d_logits + (size_t)b0 * net->n_logits : nullptr,
                            d_features ? d_features + (size_t)b0 * net->n_features : nullptr, st);
@@ -1192,6 +1252,63 @@ extern "C" int hp_net_copy_feature_map(const hp_net* net, int index, int batch, 
   const auto& f = net->feature_maps[index];
   HP_CHECK_HIP(hipMemcpyAsync(d_dst, net->bufs[f.buf].p, (size_t)batch * f.H * f.W * f.C * sizeof(float), hipMemcpyDeviceToDevice,
                               (hipStream_t)stream));
+  return HP_OK;
+}
+
+extern "C" int hp_net_n_ops(const hp_net* net) { return net && net->finalized ? (int)net->ops.size() : HP_ERR_ARG; }
+
+extern "C" int hp_net_op_info(const hp_net* net, int index, hp_op_info* info) {
+  HP_REQUIRE(net && net->finalized && info, "hp_net_op_info: network not finalized / null info");
+  HP_REQUIRE(index >= 0 && index < (int)net->ops.size(), "hp_net_op_info: no such op");
+  const Op& op = net->ops[index];
+  hp_op_info r{};
+  static_assert(OP_CONV == HP_OP_CONV && OP_MAXPOOL == HP_OP_MAXPOOL && OP_HEAD == HP_OP_HEAD && OP_DW == HP_OP_DWCONV &&
+                OP_SE == HP_OP_SE && OP_RESIZE == HP_OP_RESIZE, "OpKind and HP_OP_* share their values");
+  r.kind = (int)op.kind;
+  r.in_slot = op.in_buf; r.out_slot = op.out_buf; r.res_slot = -1;
+  r.H = op.H; r.W = op.W; r.Cin = r.Cout = op.C; r.Ho = op.Ho; r.Wo = op.Wo;
+  r.elem_bytes = net->precision == HP_PRECISION_F16 ? 2 : 4;
+  std::string name;
+  if (op.kind == OP_CONV) {
+    const ConvLayer& L = *net->convs[op.conv];
+    name = L.wname;
+    r.k = L.kh; r.stride = L.stride; r.pad = L.pad; r.act = L.relu;
+    r.H = L.H; r.W = L.W; r.Cin = L.cin_real; r.Ho = L.Ho; r.Wo = L.Wo; r.Cout = L.cout;
+    r.prologue = L.bn_before.empty() ? 0 : 1;
+    r.in_slot = L.in_buf; r.res_slot = L.res_buf; r.out_slot = L.out_buf;
+  } else if (op.kind == OP_DW) {
+    const DwLayer& D = *net->dws[op.conv];
+    name = D.wname;
+    r.k = D.k; r.stride = D.stride; r.pad = D.pad; r.act = HP_ACT_SWISH;
+    r.H = D.H; r.W = D.W; r.Cin = r.Cout = D.C; r.Ho = D.Ho; r.Wo = D.Wo;
+    r.in_slot = D.in_buf; r.out_slot = D.out_buf;
+  } else if (op.kind == OP_SE) {
+    const SeLayer& S = *net->ses[op.conv];
+    name = S.prefix;
+    r.H = S.HW; r.W = 1; r.Cin = S.C; r.Cout = S.Cse; r.in_slot = S.in_buf; r.out_slot = -1;
+  } else if (op.kind == OP_MAXPOOL) {
+    r.k = 3; r.stride = 2; r.pad = 1;
+  } else if (op.kind == OP_HEAD) {
+    r.out_slot = -1; r.Cout = net->n_features;
+  }
+  std::strncpy(r.name, name.c_str(), sizeof(r.name) - 1);
+  r.path = net->op_path[index];
+  r.materialised = net->op_mat[index];
+  *info = r;
+  return HP_OK;
+}
+
+extern "C" int hp_net_set_taps(hp_net* net, int n, const int* op_index, void* const* d_dst) {
+  HP_REQUIRE(net && net->finalized && n >= 0 && (n == 0 || (op_index && d_dst)), "hp_net_set_taps: network not finalized / bad argument");
+  std::vector<void*> taps(n ? net->ops.size() : 0, nullptr);
+  for (int i = 0; i < n; ++i) {
+    HP_REQUIRE(op_index[i] >= 0 && op_index[i] < (int)net->ops.size(), "hp_net_set_taps: no such op");
+    const OpKind k = net->ops[op_index[i]].kind;
+    HP_REQUIRE(k != OP_HEAD && k != OP_SE, "hp_net_set_taps: the head and squeeze-excitation ops have no output map");
+    HP_REQUIRE(d_dst[i], "hp_net_set_taps: null destination");
+    taps[op_index[i]] = d_dst[i];
+  }
+  net->taps.swap(taps);
   return HP_OK;
 }
 
@@ -1226,10 +1343,12 @@ extern "C" int hp_net_forward_f16in(hp_net* net, const void* d_x16, int batch, f
   HP_REQUIRE(!d_pose || net->pose_dim > 0, "hp_net_forward_f16in: network has no pose head");
   HP_REQUIRE(!d_logits || net->n_logits > 0, "hp_net_forward_f16in: network has no logits head");
   hipStream_t st = (hipStream_t)stream;
+  int rc_t = taps_allowed(net, st);
+  if (rc_t) return rc_t;
   const size_t in_stride = (size_t)net->h * net->w * net->convs[0]->cin16 * sizeof(_Float16);
   for (int b0 = 0; b0 < batch; b0 += net->max_batch) {
     const int nb = batch - b0 < net->max_batch ? batch - b0 : net->max_batch;
-    int rc = forward_chunk(net, nullptr, (const char*)d_x16 + (size_t)b0 * in_stride, nb,
+    int rc = forward_chunk(net, nullptr, (const char*)d_x16 + (size_t)b0 * in_stride, b0, nb,
                            d_pose ? d_pose + (size_t)b0 * net->pose_dim : nullptr,
                            d_logits ? d_logits + (size_t)b0 * net->n_logits : nullptr,
                            d_features ? d_features + (size_t)b0 * net->n_features : nullptr, st);

@@ -560,6 +560,38 @@ class Net:
             outs.append(t)
         return outs
 
+    def op_list(self):
+        """The ops of the network in execution order (``hp_net_op_info``), one dict each: ``kind`` (a name of
+        :data:`OP_KINDS`), ``name`` (weight name of a conv), geometry, arena slots, ``elem_bytes``, and for the LAST forward
+        ``path`` (a name of :data:`OP_PATHS`) and ``materialised``."""
+        out = []
+        n = lib().hp_net_n_ops(self.handle)
+        if n < 0:
+            check(n, "hp_net_n_ops")
+        for i in range(n):
+            info = _ffi.OpInfo()
+            check(lib().hp_net_op_info(self.handle, i, C.byref(info)), "hp_net_op_info")
+            d = {n: getattr(info, n) for n, _ in _ffi.OpInfo._fields_}
+            d.update(index=i, kind=OP_KINDS[info.kind], path=OP_PATHS[info.path], name=info.name.decode(),
+                     materialised=bool(info.materialised), prologue=bool(info.prologue))
+            out.append(d)
+        return out
+
+    def set_taps(self, op_indices, batch: int):
+        """Layer-level tests (``hp_net_set_taps``): every later forward of up to ``batch`` samples leaves the output map of the
+        ops ``op_indices`` in the returned tensors ``{index: [batch, Ho, Wo, Cout]}`` (fp32, or fp16 on an fp16 plan).  An op
+        that a fused launch never writes is not copied: see ``materialised`` of :meth:`op_list` after the forward.
+        ``set_taps([], 0)`` clears them.  For tests: the library keeps the raw addresses, and only this object's reference keeps
+        the tensors alive -- clear the taps before dropping the returned dict's tensors or reusing the network elsewhere."""
+        ops_ = self.op_list()
+        dtype = torch.float16 if self.precision == "f16" else torch.float32
+        self._taps = {i: torch.zeros((batch, ops_[i]["Ho"], ops_[i]["Wo"], ops_[i]["Cout"]), dtype=dtype, device=self.device)
+                      for i in op_indices}
+        idx = (C.c_int * len(self._taps))(*self._taps)
+        dst = (C.c_void_p * len(self._taps))(*[t.data_ptr() for t in self._taps.values()])
+        check(lib().hp_net_set_taps(self.handle, len(self._taps), idx, dst), "hp_net_set_taps")
+        return self._taps
+
     def set_profiling(self, on: bool):
         check(lib().hp_net_set_profiling(self.handle, int(on)), "hp_net_set_profiling")
         self.profiling = bool(on)
@@ -688,6 +720,10 @@ class GraphNet(Net):
 
 
 STATUS_NONFINITE, STATUS_EXACT_ONLY = 1, 2
+OP_KINDS = ("conv", "maxpool", "head", "dw", "se", "resize")  # HP_OP_*
+OP_PATHS = ("none", "split3x3", "split3x3+shortcut", "rode", "winograd", "igemm_split", "patch", "generic", "stem7_pool",  # HP_PATH_*
+            "stem7_pool_f16", "stem_split_pool", "igemm_split_pool", "mbconv_front", "fused_away", "conv_f16", "maxpool",
+            "maxpool_f16", "head", "dw", "se", "resize", "mixed")
 CONV_GATED = 0x100  # HP_CONV_GATED
 
 

@@ -394,6 +394,61 @@ int hp_net_feature_map(const hp_net* net, int index, const float** d_ptr, int* h
  * + one padding channel) and 10..14 the RPN box deltas ([h][w][12]) (torchvision models/detection/rpn.py: RPNHead, keys
  * "rpn.head.conv.0.0.*", "rpn.head.cls_logits.*", "rpn.head.bbox_pred.*"). */
 int hp_net_copy_feature_map(const hp_net* net, int index, int batch, float* d_dst, void* stream);
+/* Layer-level tests: the op list of a finalized network of any architecture, and taps on it.  The arena of a built-in plan
+ * rotates a few slots, so an intermediate map is gone after a forward; a tap keeps it.
+ *   hp_net_n_ops / hp_net_op_info: the ops in execution order.  kind HP_OP_*; name = the weight name of a convolution
+ *     ("backbone.layer2.0.conv1.weight") or depthwise layer, the prefix of a squeeze-excitation, "" otherwise; k, stride, pad,
+ *     act (HP_ACT values: 0 none, 1 ReLU, 2 swish); H, W, Cin the input map (Cin = the module's channel count), Ho, Wo, Cout the
+ *     output map as stored, NHWC [Ho][Wo][Cout]; prologue = 1 when BatchNorm + ReLU is applied to the input; in_slot / res_slot /
+ *     out_slot the arena slots read and written (-1 = the network input / none); elem_bytes 4 (fp32 plan) or 2 (fp16 plan).
+ *     A squeeze-excitation reports H = positions pooled, W = 1, Cout = its reduced width; the head has no output map.
+ *     path / materialised describe the LAST hp_net_forward: path = HP_PATH_* the launch that produced the op's output
+ *     (HP_PATH_NONE before the first forward, HP_PATH_MIXED when the chunks of a batch > max_batch took different launches);
+ *     materialised = 0 when no launch wrote the op's output map (a stem under pool fusion, an expansion under the MBConv
+ *     front): known only at run time, it depends on algorithm, precision and guard state.
+ *   hp_net_set_taps: d_dst[i] is caller-owned device memory [batch][Ho][Wo][Cout] x elem_bytes for op op_index[i];
+ *     every forward copies the op's output there (device to device, on the launch stream) right after the launch that wrote
+ *     it, all chunks of a batch > max_batch at their sample offsets; an op that is not materialised is not copied.  n = 0
+ *     clears the taps.  Taps never change which kernels are launched or their arguments.  A forward with taps set on a
+ *     stream that is capturing is refused (HP_ERR_ARG).  Taps are for tests; the predictors never set them. */
+#define HP_OP_CONV 0
+#define HP_OP_MAXPOOL 1
+#define HP_OP_HEAD 2
+#define HP_OP_DWCONV 3
+#define HP_OP_SE 4
+#define HP_OP_RESIZE 5
+#define HP_PATH_NONE 0
+#define HP_PATH_SPLIT3X3 1          /* split-fp16 3x3 kernels (conv_split.hip / conv_pp.hip) */
+#define HP_PATH_SPLIT3X3_SHORTCUT 2 /* ... carrying the block's 1x1 / stride-2 shortcut as extra work items */
+#define HP_PATH_RODE 3              /* a shortcut written by the previous op's launch */
+#define HP_PATH_WINOGRAD 4
+#define HP_PATH_IGEMM_SPLIT 5
+#define HP_PATH_PATCH 6
+#define HP_PATH_GENERIC 7
+#define HP_PATH_STEM7_POOL 8        /* 7x7 stem + ReLU + max-pool, fp32 operands as fp16 halves */
+#define HP_PATH_STEM7_POOL_F16 9    /* the same on the fp16 plan */
+#define HP_PATH_STEM_SPLIT_POOL 10  /* 5x5 run-mode stem + ReLU + max-pool */
+#define HP_PATH_IGEMM_SPLIT_POOL 11 /* any other stem + ReLU + max-pool */
+#define HP_PATH_MBCONV_FRONT 12     /* 1x1 expansion + depthwise + pooling sums */
+#define HP_PATH_FUSED_AWAY 13       /* skipped: the previous op's fused launch wrote this op's output */
+#define HP_PATH_CONV_F16 14
+#define HP_PATH_MAXPOOL 15
+#define HP_PATH_MAXPOOL_F16 16
+#define HP_PATH_HEAD 17
+#define HP_PATH_DWCONV 18
+#define HP_PATH_SE 19
+#define HP_PATH_RESIZE 20
+#define HP_PATH_MIXED 21
+typedef struct {
+  int kind, k, stride, pad, act;
+  int H, W, Cin, Ho, Wo, Cout;
+  int prologue, in_slot, res_slot, out_slot, elem_bytes;
+  int path, materialised;
+  char name[128];
+} hp_op_info;
+int hp_net_n_ops(const hp_net* net);
+int hp_net_op_info(const hp_net* net, int index, hp_op_info* info);
+int hp_net_set_taps(hp_net* net, int n, const int* op_index, void* const* d_dst);
 /* GeneralizedRCNNTransform.normalize of the detector (torchvision models/detection/transform.py: (image - mean) / std per
  * channel; MaskRCNN defaults mean (0.485, 0.456, 0.406), std (0.229, 0.224, 0.225)) fused with the layout change the conv
  * stack wants: d_images NCHW [n][3][h][w] in [0,1] (ObservationTensor.images[:, :3]) -> d_x NHWC [n][h][w][4], pad channel 0. */

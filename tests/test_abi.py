@@ -30,6 +30,20 @@ def test_header_symbols_exported():
     assert sorted(_ffi.EXPORTED_SYMBOLS) == declared
 
 
+def test_op_kind_and_path_names_follow_the_header():
+    """ops.OP_KINDS / ops.OP_PATHS name HP_OP_* / HP_PATH_* by value: same count, consecutive from 0, the last path is MIXED."""
+    from happypose_amd import ops
+
+    text = (ROOT / "include" / "happypose_amd.h").read_text()
+    kinds = [int(v) for v in re.findall(r"#define HP_OP_[A-Z]+ (\d+)", text)]
+    paths = re.findall(r"#define HP_PATH_([A-Z0-9_]+) (\d+)", text)
+    assert kinds == list(range(len(ops.OP_KINDS)))
+    assert [int(v) for _, v in paths] == list(range(len(ops.OP_PATHS)))
+    assert paths[-1][0] == "MIXED" and ops.OP_PATHS[-1] == "mixed" and ops.OP_PATHS[0] == "none"
+    for (name, _), mine in zip(paths, ops.OP_PATHS):
+        assert mine.replace("+", "_").upper().replace("DW", "DWCONV") == name, (name, mine)
+
+
 def test_no_cpu_fallback(monkeypatch, tmp_path):
     """The product path must fail loudly when the HIP library is missing."""
     from happypose_amd import _ffi

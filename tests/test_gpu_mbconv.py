@@ -384,13 +384,41 @@ def test_block_fused_front_vs_fp64_and_unfused(dev, unfused_maps, i):
     assert not np.array_equal(old["dw"], got["dw"]), "HP_NO_MBCONV_FRONT changed nothing: which kernel ran?"
 
 
+@pytest.fixture(scope="module")
+def b3_plan_blocks(dev):
+    """The 26 blocks as the op list of a finalized ``efficientnet-b3`` network at 240 x 320 states them (``hp_net_op_info``):
+    one dict per depthwise op in the form of REAL_BLOCKS, the expansion before it and the squeeze-excitation / projection after it
+    supplying cin, cse and cout."""
+    from happypose_amd import ops
+    from happypose_amd.models import pose_model_param_shapes
+    from happypose_amd.synthetic import named_weights
+
+    net = ops.Net("efficientnet-b3", 6, named_weights(pose_model_param_shapes("efficientnet-b3", 6, pose_dim=9), seed=0), max_batch=1, device=dev)
+    ol = net.op_list()
+    blocks = []
+    for i, o in enumerate(ol):
+        if o["kind"] != "dw":
+            continue
+        se, proj, prev = ol[i + 1], ol[i + 2], ol[i - 1]
+        assert se["kind"] == "se" and proj["kind"] == "conv" and proj["name"].endswith("._project_conv.weight")
+        assert o["pad"] == SAME_PAD[(o["k"], o["stride"])][0] and se["H"] == o["Ho"] * o["Wo"] and se["Cin"] == o["Cin"]
+        c = dict(k=o["k"], s=o["stride"], H=o["H"], W=o["W"], C=o["Cin"], cout=proj["Cout"], cse=se["Cout"], n=3,
+                 skip=proj["res_slot"] >= 0)
+        if prev["kind"] == "conv" and prev["name"].endswith("._expand_conv.weight"):
+            c["cin"] = prev["Cin"]
+        blocks.append((c, (o["Ho"], o["Wo"])))
+    return blocks
+
+
 @pytest.mark.parametrize("i", range(len(REAL_BLOCKS)), ids=[f"b{i}_" + case_id(c) for i, c in enumerate(REAL_BLOCKS)])
-def test_real_block_geometries_vs_fp64(dev, i):
-    """d. each of the 26 blocks of EfficientNet-b3 at its map size in the 240 x 320 plan, batch 3.  (The ABI does not expose a
-    finalized network's per-block sizes: they follow the eff_same_pad rule here, and the last one must be the 7 x 10 of the
-    network's feature map.)"""
+def test_real_block_geometries_vs_fp64(dev, b3_plan_blocks, i):
+    """d. each of the 26 blocks of EfficientNet-b3 at its map size in the 240 x 320 plan, batch 3.  The sizes follow the
+    eff_same_pad rule here AND are read from the op list of a finalized network: the two must agree block by block, and the
+    last one must be the 7 x 10 of the network's feature map."""
     assert len(REAL_BLOCKS) == 26 and REAL_LAST == (7, 10)
     assert [(c["H"], c["W"]) for c in REAL_BLOCKS[:2] + REAL_BLOCKS[2:3]] == [(120, 160)] * 3
+    assert len(b3_plan_blocks) == 26 and b3_plan_blocks[i][0] == REAL_BLOCKS[i], (b3_plan_blocks[i][0], REAL_BLOCKS[i])
+    assert b3_plan_blocks[-1][1] == REAL_LAST
     p = make_params(REAL_BLOCKS[i], seed=100 + i)
     expanded = "cin" in REAL_BLOCKS[i]
     check_block(p, run_case(p, dev), "real", 1 if expanded else 0, 2 if expanded else 1)

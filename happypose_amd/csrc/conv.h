@@ -106,7 +106,23 @@ struct ConvArgsH {
   int tiles_m, tiles_n;       // filled by the launcher
   FastDiv fd_howo, fd_wo, fd_tn;  // by Ho*Wo, Wo, tiles_n (filled by the launcher; M < 2^31)
   int no_tail_split;          // as ConvArgs::no_tail_split
+  unsigned* status;           // as ConvArgs::status: host-visible word or null; the epilogue stores 1 when a value it
+                              // stores was inf / NaN before the activation or is non-finite as the half it became
 };
+
+#ifdef __HIPCC__
+// Non-finite guard of the fp16 plan.  Every epilogue keeps two running values per thread over what it stores (rows
+// m < M only): `chk`, the SUM of the fp32 values BEFORE the activation (inf / NaN are sticky in a sum, and ReLU would
+// turn a NaN into 0), and `amax`, the largest |value| AFTER bias, residual and activation.  A finite fp32 value rounds
+// (to nearest even) to a non-finite half exactly when its magnitude reaches 65520 = 65504 + half an ulp, so the
+// comparison below is the test "the half as stored is inf" without reading the half back.  One compare and, in the
+// failure case only, one store per thread.
+constexpr float kHalfOverflow = 65520.f;
+__device__ __forceinline__ void conv_report_nonfinite_f16(unsigned* status, float chk, float amax) {
+  if (status && (!(fabsf(chk) <= 3.0e38f) || !(amax < kHalfOverflow)))
+    __hip_atomic_store(status, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+}
+#endif
 
 // depthwise k x k conv + folded BN + swish (mbconv.hip)
 struct DwArgs {

@@ -59,6 +59,27 @@ __device__ __forceinline__ halfx8 load8(__amdgpu_buffer_rsrc_t r, unsigned voff,
   return __builtin_bit_cast(halfx8, __builtin_amdgcn_raw_buffer_load_b128(r, (int)voff, (int)soff, 0));
 }
 
+// The guard word is read from the kernarg segment where it is used (through a laundered pointer, as conv_pp.hip's
+// opaque_args; ConvArgsH is the first kernel argument): held in SGPRs from the kernel's head it cost the patch kernels
+// two more SGPR spills each.
+__device__ __forceinline__ unsigned* guard_word(const ConvArgsH& a) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  typedef const __attribute__((address_space(4))) ConvArgsH* KArgs;
+  KArgs p = (KArgs)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(p));
+  return p->status;
+#else  // host pass of the single-source compile: never executed
+  return a.status;
+#endif
+}
+
+// running max |v| over the 8 values of a stored piece: four v_max3_f32 with |.| source modifiers
+__device__ __forceinline__ float epi_amax8(float amax, const floatx4& v0, const floatx4& v1) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) amax = fmaxf(fmaxf(amax, fabsf(v0[q])), fabsf(v1[q]));
+  return amax;
+}
+
 template <int BN, bool PRE>
 __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))) void conv_igemm_f16(ConvArgsH a) {
   constexpr int WM = BM / 2, WN = BN / 2, MT = WM / 32, NT = WN / 32;
@@ -228,6 +249,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     b0 = *reinterpret_cast<const floatx4*>(a.bias + n);
     b1 = *reinterpret_cast<const floatx4*>(a.bias + n + 4);
   }
+  float chk = 0.f, amax = 0.f;  // non-finite guard (conv_report_nonfinite_f16)
 #pragma unroll
   for (int k = 0; k < ITERS; ++k) {
     const int row = tid / C8 + k * (kThreads / C8);
@@ -240,16 +262,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
         for (int q = 0; q < 4; ++q) { v0[q] += (float)rr[q]; v1[q] += (float)rr[4 + q]; }
       }
+      chk += ((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3]));
       if (a.relu) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) { v0[q] = fmaxf(v0[q], 0.f); v1[q] = fmaxf(v1[q], 0.f); }
       }
+      amax = epi_amax8(amax, v0, v1);
       halfx8 o;
 #pragma unroll
       for (int q = 0; q < 4; ++q) { o[q] = (_Float16)v0[q]; o[4 + q] = (_Float16)v1[q]; }
       *reinterpret_cast<halfx8*>(a.y + m * a.Cout + n) = o;
     }
   }
+  conv_report_nonfinite_f16(guard_word(a), chk, amax);
 }
 
 // ---- 3x3 / stride-1 / pad-1 layers: input staged ONCE per 64-channel chunk ("patch" variant, as
@@ -446,6 +471,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
     b0 = *reinterpret_cast<const floatx4*>(a.bias + n);
     b1 = *reinterpret_cast<const floatx4*>(a.bias + n + 4);
   }
+  float chk = 0.f, amax = 0.f;  // non-finite guard (conv_report_nonfinite_f16)
 #pragma unroll
   for (int k = 0; k < ITERS; ++k) {
     const int row = tid / C8 + k * (kThreads / C8);
@@ -458,16 +484,19 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
 #pragma unroll
         for (int q = 0; q < 4; ++q) { v0[q] += (float)rr[q]; v1[q] += (float)rr[4 + q]; }
       }
+      chk += ((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3]));
       if (a.relu) {
 #pragma unroll
         for (int q = 0; q < 4; ++q) { v0[q] = fmaxf(v0[q], 0.f); v1[q] = fmaxf(v1[q], 0.f); }
       }
+      amax = epi_amax8(amax, v0, v1);
       halfx8 o;
 #pragma unroll
       for (int q = 0; q < 4; ++q) { o[q] = (_Float16)v0[q]; o[4 + q] = (_Float16)v1[q]; }
       *reinterpret_cast<halfx8*>(a.y + m * a.Cout + n) = o;
     }
   }
+  conv_report_nonfinite_f16(guard_word(a), chk, amax);
 }
 
 template <int BN, bool PRE, int NPC>
@@ -537,6 +566,8 @@ int launch_variant(ConvArgsH args, hipStream_t stream) {
 }
 
 // ---- network input: fp32 NHWC [.., c_in] -> fp16 NHWC [.., c_out] (c_out >= c_in, zero padded) ----
+// No guard of its own: an input beyond the fp16 range becomes inf here, and the stem conv that reads it reports the inf /
+// NaN accumulators it makes of it (ConvArgsH::status); the same holds for an fp16 input record that already holds one.
 __global__ __launch_bounds__(256) void cast_pad_f32_f16(const float* x, _Float16* y, int64_t pixels, int c_in, int c_out) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;  // one 8-half chunk of y each
   const int c8 = c_out / 8;
@@ -550,6 +581,7 @@ __global__ __launch_bounds__(256) void cast_pad_f32_f16(const float* x, _Float16
 }
 
 // ---- 3x3 stride-2 pad-1 max pooling, NHWC fp16, 8 channels per lane ----
+// No guard of its own: it moves halves that the stem conv stored, and that launch has reported any non-finite one.
 __global__ __launch_bounds__(256) void maxpool3x3s2_nhwc_f16(const _Float16* x, _Float16* y, int n, int H, int W, int C,
                                                              int Ho, int Wo) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;

@@ -230,16 +230,32 @@ __device__ __forceinline__ void pp_epilogue_direct(const ConvArgs& a, pp_floatx1
 #pragma unroll
           for (int q = 0; q < 4; ++q) { v0[q] += (float)rr[q]; v1[q] += (float)rr[4 + q]; }
         }
-        if (a.relu) {
-          v0 = __builtin_elementwise_max(v0, pp_floatx4{0.f, 0.f, 0.f, 0.f});
-          v1 = __builtin_elementwise_max(v1, pp_floatx4{0.f, 0.f, 0.f, 0.f});
-        }
-        pp_halfx8 o;
+        // non-finite guard of the fp16 plan (conv.h: conv_report_nonfinite_f16), rows m < M only: the sum of the piece before
+        // the activation, the largest magnitude after it
+        if (m < a.M) {
+          chk += ((v0[0] + v0[1]) + (v0[2] + v0[3])) + ((v1[0] + v1[1]) + (v1[2] + v1[3]));
+          if (a.relu) {
+            v0 = __builtin_elementwise_max(v0, pp_floatx4{0.f, 0.f, 0.f, 0.f});
+            v1 = __builtin_elementwise_max(v1, pp_floatx4{0.f, 0.f, 0.f, 0.f});
+          }
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { o[q] = (_Float16)v0[q]; o[4 + q] = (_Float16)v1[q]; }
-        if (m < a.M) *reinterpret_cast<pp_halfx8*>(y + m * a.Cout + n) = o;
+          for (int q = 0; q < 4; ++q) amax = fmaxf(fmaxf(amax, fabsf(v0[q])), fabsf(v1[q]));
+          pp_halfx8 o;
+#pragma unroll
+          for (int q = 0; q < 4; ++q) { o[q] = (_Float16)v0[q]; o[4 + q] = (_Float16)v1[q]; }
+          *reinterpret_cast<pp_halfx8*>(y + m * a.Cout + n) = o;
+        }
       }
     }
+    // the guard word is fetched from the kernarg segment here, at its one use (a laundered pointer, as opaque_args below;
+    // ConvArgs is the first argument of the only kernel that instantiates this branch): two SGPRs less across the epilogue
+#if defined(__HIP_DEVICE_COMPILE__)
+    const __attribute__((address_space(4))) ConvArgs* ka = (const __attribute__((address_space(4))) ConvArgs*)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(ka));
+    conv_report_nonfinite_f16(ka->status, chk, amax);
+#else
+    conv_report_nonfinite_f16(a.status, chk, amax);
+#endif
   }
 }
 
@@ -1046,7 +1062,7 @@ int launch_conv_pp_f16(const ConvArgsH& h, hipStream_t stream) {
   a.pre_scale = reinterpret_cast<const float*>(h.pre_scale); a.pre_shift = reinterpret_cast<const float*>(h.pre_shift);
   a.y = reinterpret_cast<float*>(h.y);
   a.M = h.M; a.H = h.H; a.W = h.W; a.Cin = h.Cin; a.Ho = h.Ho; a.Wo = h.Wo; a.Cout = h.Cout; a.stride = 1; a.pad = 1;
-  a.Kpad = h.Kpad; a.relu = h.relu; a.no_tail_split = h.no_tail_split;
+  a.Kpad = h.Kpad; a.relu = h.relu; a.no_tail_split = h.no_tail_split; a.status = h.status;
   if (pp_f16_wide64_ok(h))
     return h.pre_scale ? launch_pp_variant<MODE_F16, true, 11, 2, true>(a, stream) : launch_pp_variant<MODE_F16, false, 11, 2, true>(a, stream);
   return h.pre_scale ? launch_pp_nt<MODE_F16, true, 2>(a, stream) : launch_pp_nt<MODE_F16, false, 2>(a, stream);

@@ -32,6 +32,7 @@ namespace hp {
 
 typedef _Float16 s7_halfx8 __attribute__((ext_vector_type(8)));
 typedef _Float16 s7_halfx4 __attribute__((ext_vector_type(4)));
+typedef _Float16 s7_halfx2 __attribute__((ext_vector_type(2)));
 typedef float s7_floatx16 __attribute__((ext_vector_type(16)));
 typedef float s7_floatx4 __attribute__((ext_vector_type(4)));
 
@@ -261,7 +262,7 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
   __syncthreads();
   constexpr int C4 = BN / 4;
   const int Hp = (a.Ho - 1) / 2 + 1, Wp = (a.Wo - 1) / 2 + 1;
-  float pool_chk = 0.f;
+  float pool_chk = 0.f, pool_amax = 0.f;
 #pragma unroll
   for (int it0 = 0; it0 < PR * PC * C4; it0 += kThreads) {
     const int it = it0 + tid;
@@ -288,10 +289,14 @@ __global__ __launch_bounds__(kThreads) __attribute__((amdgpu_waves_per_eu(2, 2))
       *reinterpret_cast<s7_floatx4*>(a.y + o) = best;
     } else {
       *reinterpret_cast<s7_halfx4*>(reinterpret_cast<_Float16*>(a.y) + o) = __builtin_convertvector(best, s7_halfx4);
+      pool_amax = fmaxf(fmaxf(pool_amax, fmaxf(best[0], best[1])), fmaxf(best[2], best[3]));  // after ReLU: no |.| needed
     }
     pool_chk += (seen[0] + seen[1]) + (seen[2] + seen[3]);
   }
+  // fp16 plan: the window sums catch inf / NaN accumulators (an inf input, inf weights; the bias is added to the window's
+  // maximum, a finite + finite sum that can only overflow the HALF), pool_amax the pooled value that rounds to inf
   if (MODE == MODE_SPLIT) conv_report_nonfinite(a, pool_chk);
+  else conv_report_nonfinite_f16(a.status, pool_chk, pool_amax);
 }
 
 template <int MODE, int SC>
@@ -502,16 +507,26 @@ __global__ __launch_bounds__(s7p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
     if (te.ok) {
       unsigned char* const Ew = Grp + wl * 64 * EPITCH;
       const int oh0 = 2 * PR * te.ty - 1, ow0 = 2 * PC * te.tx - 1 + 8 * wl;
+      // non-finite guard, reported per tile (this persistent kernel has no registers to carry it to its end): the sum of
+      // what the lane's conv pixels hold before the ReLU.  Only pixels inside the map feed a stored value (every one of
+      // them lies in some stored window); the block's pixels beyond the map's edge are computed from whatever the staged
+      // region holds and must not raise the flag
+      float guard_chk = 0.f, guard_max = 0.f;
 #pragma unroll
       for (int nt = 0; nt < 2; ++nt)
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
           s7_halfx8 o[2];
+          float pre = 0.f;
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const float v = fmaxf(acc[mt][nt][r] + bias_r[nt][r >> 2][r & 3], 0.f);
+            const float u = acc[mt][nt][r] + bias_r[nt][r >> 2][r & 3];
+            pre += u;
+            const float v = fmaxf(u, 0.f);
             o[r >> 3][r & 7] = (_Float16)v;
           }
+          const int dr = pix[mt] / 9, dcl = pix[mt] - 9 * dr;
+          if ((unsigned)(oh0 + dr) < (unsigned)a.Ho && (unsigned)(ow0 + dcl) < (unsigned)a.Wo) guard_chk += pre;
           unsigned char* const dst = Ew + pix[mt] * EPITCH + 64 * nt + 32 * hsel;
           *reinterpret_cast<s7_halfx8*>(dst) = o[0];
           *reinterpret_cast<s7_halfx8*>(dst + 16) = o[1];
@@ -541,9 +556,14 @@ __global__ __launch_bounds__(s7p::kT) __attribute__((amdgpu_waves_per_eu(2, 2)))
 #pragma unroll
             for (int k = 1; k < 9; ++k) best = __builtin_elementwise_max(best, v[k]);
             *reinterpret_cast<s7_halfx8*>(yg + (((int64_t)te.img * Hp + ph) * Wp + pw) * BN + 8 * c8) = best;
+            // the halves as stored (>= 0 after the ReLU): their maximum is inf when one of them overflowed
+            const s7_halfx4 b4 = __builtin_elementwise_max(best.lo, best.hi);
+            const s7_halfx2 b2 = __builtin_elementwise_max(b4.lo, b4.hi);
+            guard_max = fmaxf(guard_max, (float)(b2[0] > b2[1] ? b2[0] : b2[1]));
           }
         }
       }
+      conv_report_nonfinite_f16(a.status, guard_chk, guard_max);
     }
     lds_barrier();  // every wave of the group is done with the epilogue tile: the input region may be overwritten
     if (ts.ok) {

@@ -891,7 +891,8 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
   if (net->h_status && *(volatile unsigned*)net->h_status) {
     hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
     (void)hipStreamIsCapturing((hipStream_t)stream, &cap);
-    if (cap == hipStreamCaptureStatusNone) net->exact_only = true;
+    // (an fp16 network has no exact kernels of its own and never latches: its flag is the caller's to act on, hp_net_status)
+    if (cap == hipStreamCaptureStatusNone && !f16) net->exact_only = true;
   }
   const int net_algo = net->exact_only ? HP_CONV_ALGO_WINOGRAD : (net->algo >= 0 ? net->algo : HP_CONV_ALGO_AUTO);
   if (!f16 && (rc = ensure_wino_weights(net, net_algo, stream))) return rc;
@@ -963,6 +964,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       a.stride = L.stride; a.pad = L.pad; a.Kpad = L.Kpad16; a.ktiles = L.Kpad16 / 64; a.relu = L.relu;
       a.kh = L.kh; a.kw = L.kw;
       a.no_tail_split = net->tail_split ? 0 : 1;
+      a.status = net->d_status;  // every fp16 launch that writes activations reports into the network's guard word
       a.x_bytes = (int64_t)batch * L.H * L.W * L.cin16 * 2;
       a.w_bytes = (int64_t)L.cout * L.Kpad16 * 2;
       if ((rc = prof_begin(op.conv))) return rc;
@@ -974,6 +976,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
         s7.x = (const float*)a.x; s7.w = (const float*)L.w_stem7.p; s7.bias = a.bias; s7.y = (float*)net->bufs[next16->out_buf].p;
         s7.M = a.M; s7.H = L.H; s7.W = L.W; s7.Cin = L.cin16; s7.Ho = L.Ho; s7.Wo = L.Wo; s7.Cout = L.cout; s7.relu = L.relu;
         s7.Kpad = L.cin_real;  // selects the kernel the weights were packed for
+        s7.status = a.status;
         if ((rc = launch_conv_stem7_pool(s7, 1, stream))) return rc;
         pool_fused = true; written = false;
         note(oi, HP_PATH_STEM7_POOL_F16, false);
@@ -1180,6 +1183,7 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       note(oi, HP_PATH_MAXPOOL);
     } else {
       if ((rc = prof_end(true))) return rc;
+      // (fp16 plan: the head reads halves that the last conv stored and reported on, and accumulates in fp32: no guard of its own)
       HeadArgs h{};
       h.x = net->bufs[op.in_buf].p; h.x_is_half = f16 ? 1 : 0; h.HW = op.H * op.W; h.C = op.C;
       h.fc_w = (const float*)net->fc_w.p; h.fc_b = (const float*)net->fc_b.p;
@@ -1446,12 +1450,15 @@ extern "C" int hp_net_status(hp_net* net, void* stream, int* flags) {
   *flags = 0;
   if (!net->finalized) return HP_OK;
   HP_CHECK_HIP(hipStreamSynchronize((hipStream_t)stream));
+  const bool f16 = net->precision == HP_PRECISION_F16;
   if (*(volatile unsigned*)net->h_status) {
     *flags |= HP_STATUS_NONFINITE;
-    net->exact_only = true;  // a re-run of the same inputs takes the exact-fp32 kernels
+    // a re-run of the same inputs takes the exact-fp32 kernels; an fp16 network has none: the caller repeats the stage on
+    // an HP_PRECISION_F32 network of the same parameters (happypose_amd.ops.Net does)
+    if (!f16) net->exact_only = true;
     *(volatile unsigned*)net->h_status = 0u;
   }
-  if (net->exact_only) *flags |= HP_STATUS_EXACT_ONLY;
+  if (net->exact_only && !f16) *flags |= HP_STATUS_EXACT_ONLY;
   return HP_OK;
 }
 

@@ -118,7 +118,9 @@ def default_coarse_precision(model_name: str) -> str:
     """``"f16"`` for the multi-hypothesis configurations (BASELINE.json config 5 names fp16 for exactly this stage: 576 grid views
     per object are SCORED and the five best kept -- the fp16 plan's logits stay within 0.05 of the oracle's spread over an
     object's grid poses and pick the same five, ``tests/test_gpu_pipeline.py::test_c5_coarse_scoring_vs_oracle``), ``"f32"`` for
-    the single-hypothesis ones, whose coarse winner alone seeds the refiner."""
+    the single-hypothesis ones, whose coarse winner alone seeds the refiner.  The fp16 default is guarded: an activation
+    that leaves the fp16 range inside the network is reported by the fp16 kernels and the stage is repeated on an fp32 sibling
+    network (``ops.Net.status``, ``tests/test_gpu_f16_guard.py``)."""
     return "f16" if NAMED_MODELS[model_name]["inference_parameters"]["n_pose_hypotheses"] > 1 else "f32"
 
 

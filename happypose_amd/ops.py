@@ -46,6 +46,11 @@ def bump_graph_epoch() -> None:
     _GRAPH_EPOCH += 1
 
 
+def _stream_capturing() -> bool:
+    """Is the current stream capturing a graph?  (False before the GPU runtime was initialised: nothing can capture then.)"""
+    return torch.cuda.is_initialized() and torch.cuda.is_current_stream_capturing()
+
+
 def _np_ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
@@ -474,6 +479,13 @@ class Net:
     profiling = False  # set_profiling(True): conv stretches are timed with HIP events (no graph capture then)
     tail_split = True  # hp_net_set_tail_split state: changes the launch plan, so it is part of a graph signature
     _exact_only = False  # last seen HP_STATUS_EXACT_ONLY (the guard's switch to the exact-fp32 kernels)
+    # An fp16 plan has no exact kernels of its own: its remedy is an fp32 SIBLING -- an ``ops.Net`` of the same parameters
+    # and geometry with ``precision="f32"``, forced exact -- built the first time the guard fires (``status``) or
+    # ``force_exact(True)`` is called, and used for everything until ``force_exact(False)``.  It costs a second set of
+    # weights and a second activation arena at ``max_batch``, which is why it is not built before it is needed.
+    _sibling: Optional["Net"] = None
+    _on_sibling = False
+    _host_params = None  # fp16 plan: the parameters on the host, what the sibling is built from
 
     def __init__(self, arch: str, n_inputs: int, state_dict: Dict[str, "np.ndarray | torch.Tensor"],
                  max_batch: int = 128, device="cuda", h: int = 240, w: int = 320, precision: str = "f32"):
@@ -488,6 +500,7 @@ class Net:
             self._h = lib().hp_net_create(ARCH[arch], n_inputs, h, w)
             if not self._h:
                 raise _ffi.HipLibraryError("hp_net_create: " + lib().hp_last_error().decode())
+            keep = {} if precision == "f16" else None
             for name, value in state_dict.items():
                 if name.endswith("num_batches_tracked"):
                     continue
@@ -495,9 +508,13 @@ class Net:
                 arr = np.ascontiguousarray(arr, dtype=np.float32)
                 check(lib().hp_net_set_param(self.handle, name.encode(), _np_ptr(arr), arr.size),
                       f"hp_net_set_param({name})")
+                if keep is not None:
+                    keep[name] = arr.copy()  # the caller's tensors may change or go away before the sibling is built
+            self._host_params = keep
             check(lib().hp_net_set_precision(self.handle, {"f32": 0, "f16": 1}[precision]), "hp_net_set_precision")
             check(lib().hp_net_finalize(self.handle, max_batch), "hp_net_finalize")
         self.c_pad = lib().hp_net_input_channels_padded(self.handle)
+        self.c16 = lib().hp_net_input_channels_f16(self.handle) if precision == "f16" else 0  # channels of an fp16 input record
         self.pose_dim = state_dict["pose_fc.weight"].shape[0] if "pose_fc.weight" in state_dict else 0
         self.n_logits = (state_dict["views_logits_head.weight"].shape[0]
                          if "views_logits_head.weight" in state_dict else 0)
@@ -515,22 +532,63 @@ class Net:
     def handle(self):
         return C.c_void_p(self._h)
 
+    def _exact_net(self) -> "Net":
+        """The fp32 sibling of an fp16 plan, built on first use.  Building allocates (weights, an activation arena), so
+        it only happens at the guard's synchronisation points -- never while a stream captures."""
+        assert self.precision == "f16" and self._host_params is not None
+        if self._sibling is None:
+            assert not _stream_capturing(), "the fp32 sibling of an fp16 network cannot be built while a stream captures"
+            sib = Net(self.arch, self.n_inputs, self._host_params, max_batch=self.max_batch, device=self.device,
+                      h=self.h, w=self.w, precision="f32")
+            # the repeat is the reference's arithmetic, not the split-fp16 kernels: exact from the start (set on the handle, not
+            # through force_exact(): the switch-over is ONE launch-plan change and bumps the graph epoch once)
+            check(lib().hp_net_force_exact(sib.handle, 1), "hp_net_force_exact")
+            sib._exact_only = True
+            if not self.tail_split:
+                sib.set_tail_split(False)
+            if self.profiling:
+                check(lib().hp_net_set_profiling(sib.handle, 1), "hp_net_set_profiling")
+                sib.profiling = True
+            self._sibling = sib
+        return self._sibling
+
+    def _switch(self, on: bool) -> None:
+        """Send every later call to the fp32 sibling (``on``) or back to the fp16 plan; a transition changes the launch
+        plan, so it bumps the graph epoch."""
+        assert not _stream_capturing(), "the numerical guard is consulted outside graph captures"
+        if on:
+            self._exact_net()
+        if on != self._on_sibling:
+            bump_graph_epoch()
+        self._on_sibling = self._exact_only = on
+
+    def input_spec(self) -> Tuple[torch.dtype, int]:
+        """``(dtype, channels)`` of the record :meth:`new_input` makes NOW (an fp16 plan that fell back to its fp32
+        sibling takes fp32 records)."""
+        if self._on_sibling:
+            return self._sibling.input_spec()
+        return (torch.float16, self.c16) if self.precision == "f16" else (torch.float32, self.c_pad)
+
     def new_input(self, batch: int) -> torch.Tensor:
         """Zeroed NHWC input buffer (pad channels must stay 0): fp32 ``[batch,h,w,c_pad]``, or for an
         fp16 plan fp16 ``[batch,h,w,c16]`` -- crop and rasteriser write it directly and ``forward``
         skips the conversion pass (``hp_net_forward_f16in``)."""
+        if self._on_sibling:
+            return self._sibling.new_input(batch)
         if self.precision == "f16":
-            c16 = lib().hp_net_input_channels_f16(self.handle)
-            assert c16 > 0, lib().hp_last_error().decode()
-            return torch.zeros((batch, self.h, self.w, c16), dtype=torch.float16, device=self.device)
+            assert self.c16 > 0, lib().hp_last_error().decode()
+            return torch.zeros((batch, self.h, self.w, self.c16), dtype=torch.float16, device=self.device)
         return torch.zeros((batch, self.h, self.w, self.c_pad), dtype=torch.float32, device=self.device)
 
     def forward(self, x: torch.Tensor, want_pose=True, want_logits=False, want_features=False):
+        if self._on_sibling:
+            assert x.dtype == torch.float32, "this fp16 network runs on its fp32 sibling now: take the input from new_input()"
+            return self._sibling.forward(x, want_pose=want_pose, want_logits=want_logits, want_features=want_features)
         b = x.shape[0]
         f = dict(dtype=torch.float32, device=self.device)
         if x.dtype == torch.float16:
             assert self.precision == "f16" and x.is_contiguous() and x.shape[:3] == (b, self.h, self.w)
-            assert x.shape[3] == lib().hp_net_input_channels_f16(self.handle)
+            assert x.shape[3] == self.c16
             pose = torch.empty((b, self.pose_dim), **f) if (want_pose and self.pose_dim) else None
             logits = torch.empty((b, self.n_logits), **f) if (want_logits and self.n_logits) else None
             feats = torch.empty((b, self.n_features), **f) if want_features else None
@@ -564,6 +622,8 @@ class Net:
         """The ops of the network in execution order (``hp_net_op_info``), one dict each: ``kind`` (a name of
         :data:`OP_KINDS`), ``name`` (weight name of a conv), geometry, arena slots, ``elem_bytes``, and for the LAST forward
         ``path`` (a name of :data:`OP_PATHS`) and ``materialised``."""
+        if self._on_sibling:
+            return self._sibling.op_list()
         out = []
         n = lib().hp_net_n_ops(self.handle)
         if n < 0:
@@ -583,6 +643,8 @@ class Net:
         that a fused launch never writes is not copied: see ``materialised`` of :meth:`op_list` after the forward.
         ``set_taps([], 0)`` clears them.  For tests: the library keeps the raw addresses, and only this object's reference keeps
         the tensors alive -- clear the taps before dropping the returned dict's tensors or reusing the network elsewhere."""
+        if self._on_sibling:
+            return self._sibling.set_taps(op_indices, batch)
         ops_ = self.op_list()
         dtype = torch.float16 if self.precision == "f16" else torch.float32
         self._taps = {i: torch.zeros((batch, ops_[i]["Ho"], ops_[i]["Wo"], ops_[i]["Cout"]), dtype=dtype, device=self.device)
@@ -593,6 +655,9 @@ class Net:
         return self._taps
 
     def set_profiling(self, on: bool):
+        if self._sibling is not None:  # both plans follow, so that the switch is the same on either side of a fallback
+            check(lib().hp_net_set_profiling(self._sibling.handle, int(on)), "hp_net_set_profiling")
+            self._sibling.profiling = bool(on)
         check(lib().hp_net_set_profiling(self.handle, int(on)), "hp_net_set_profiling")
         self.profiling = bool(on)
         bump_graph_epoch()  # event records change the launch sequence a captured graph holds
@@ -606,6 +671,8 @@ class Net:
     def set_tail_split(self, on: bool):
         """K-slicing of the tail tiles of this network's conv launches (``hp_net_set_tail_split``): off while a
         second lane shares the GPU."""
+        if self._sibling is not None:
+            self._sibling.set_tail_split(on)
         check(lib().hp_net_set_tail_split(self.handle, int(on)), "hp_net_set_tail_split")
         self.tail_split = bool(on)
 
@@ -618,11 +685,23 @@ class Net:
         """``hp_net_status``: waits for ``stream`` (default: the current one) and returns the guard flags --
         bit 0 (:data:`STATUS_NONFINITE`): a forward since the last call produced inf / NaN in a split-fp16
         layer (an activation beyond the fp16 range), its outputs are invalid; bit 1 (:data:`STATUS_EXACT_ONLY`):
-        the network now runs the exact-fp32 kernels only, so re-running the same inputs is valid."""
+        the network now runs the exact-fp32 kernels only, so re-running the same inputs is valid.
+
+        An fp16 plan reports bit 0 when a value one of its layers stored was inf / NaN before the activation or
+        overflowed the half it was rounded to.  It then builds its fp32 sibling, sends every later call there and
+        returns ``STATUS_NONFINITE | STATUS_EXACT_ONLY`` for this call and ``STATUS_EXACT_ONLY`` afterwards -- the
+        same contract, sticky until ``force_exact(False)``.  Not to be called while a stream captures."""
+        if self._on_sibling:
+            return self._sibling.status(stream) | STATUS_EXACT_ONLY
         flags = C.c_int(0)
         sp = stream_ptr(self.device) if stream is None else C.c_void_p(stream.cuda_stream)
         with torch.cuda.device(self.device):
             check(lib().hp_net_status(self.handle, sp, C.byref(flags)), "hp_net_status")
+        if self.precision == "f16":  # the library never latches an fp16 network: the fallback is this object's
+            if flags.value & STATUS_NONFINITE:
+                self._switch(True)
+                return flags.value | STATUS_EXACT_ONLY
+            return flags.value
         exact = bool(flags.value & STATUS_EXACT_ONLY)
         if (flags.value & STATUS_NONFINITE) or exact != self._exact_only:
             # the network switched kernels (or just poisoned a forward): captured graphs still hold the old launches.
@@ -633,7 +712,12 @@ class Net:
         return flags.value
 
     def force_exact(self, on: bool = True) -> None:
-        """``hp_net_force_exact``: put the network on (or take it off) the exact-fp32 kernels the guard switches to."""
+        """``hp_net_force_exact``: put the network on (or take it off) the exact-fp32 kernels the guard switches to.
+        An fp16 plan goes to (returns from) its fp32 sibling instead; input records change dtype with it
+        (:meth:`input_spec`).  Not to be called while a stream captures."""
+        if self.precision == "f16":
+            self._switch(bool(on))
+            return
         check(lib().hp_net_force_exact(self.handle, int(bool(on))), "hp_net_force_exact")
         if bool(on) != self._exact_only:
             bump_graph_epoch()
@@ -644,6 +728,8 @@ class Net:
         the last call (HIP events on the launch stream; waits for them): algorithmic FLOPs of the
         direct convolutions and FLOPs the matrix cores executed (Winograd layers execute 2.25x
         fewer, padded tiles more)."""
+        if self._on_sibling:
+            return self._sibling.profile_collect()
         ms, n, fl, mfl = C.c_double(0), C.c_int64(0), C.c_double(0), C.c_double(0)
         check(lib().hp_net_profile_collect(self.handle, C.byref(ms), C.byref(n), C.byref(fl), C.byref(mfl)),
               "hp_net_profile_collect")
@@ -652,6 +738,8 @@ class Net:
     def profile_intervals(self):
         """``[(t0_ms, t1_ms), ...]`` of the timed conv stretches pending for this network, relative to
         :func:`profile_mark_reference` (call before :meth:`profile_collect`)."""
+        if self._on_sibling:
+            return self._sibling.profile_intervals()
         n = lib().hp_net_profile_intervals(self.handle, None, None, 0)
         if n < 0:
             check(n, "hp_net_profile_intervals")

@@ -128,8 +128,13 @@ class _RenderAndCompare:
         return self
 
     def _input_buffer(self, b: int) -> torch.Tensor:
+        # an fp16 backbone whose guard fired runs on its fp32 sibling (ops.Net.input_spec changes with it): the record is
+        # re-made, so that crop and rasteriser write fp32 for the repeat (and fp16 again after force_exact(False))
+        rows = b
+        if self._x is not None and (self._x.dtype, self._x.shape[3]) != tuple(self.backbone.input_spec()):
+            rows, self._x = max(b, self._x.shape[0]), None  # as large as the record it replaces: no second growth later
         if self._x is None or self._x.shape[0] < b:
-            self._x = self.backbone.new_input(b)  # zeroed once: pad channels are never written
+            self._x = self.backbone.new_input(rows)  # zeroed once: pad channels are never written
         return self._x[:b]
 
     def _ids(self, images, K, labels, im_ids):

@@ -511,7 +511,13 @@ int hp_net_set_act_scale(hp_net* net, int enabled);
  *   HP_STATUS_EXACT_ONLY the network has switched to the exact-fp32 kernels (Winograd / direct; sticky): re-running
  *                        the same inputs now gives the reference's arithmetic.
  * hp_net_forward also reads the word (without synchronising) on entry, so once a completed forward has tripped the
- * guard every later forward runs on the exact kernels by itself. */
+ * guard every later forward runs on the exact kernels by itself.
+ * HP_PRECISION_F16 networks are covered too: every fp16 launch that writes activations (stems, 1x1, 3x3, stride 2) sets
+ * HP_STATUS_NONFINITE when a value it stores was inf / NaN in fp32 BEFORE the activation (ReLU would hide a NaN) or is
+ * non-finite as the half it was rounded to; hp_net_status returns and clears it as above.  An fp16 network has no exact
+ * kernels of its own: it never reports HP_STATUS_EXACT_ONLY, does not latch, and hp_net_force_exact is accepted without
+ * effect.  The remedy is the caller's: run the stage again on an HP_PRECISION_F32 network of the same parameters (the
+ * Python layer, happypose_amd.ops.Net, keeps such a sibling and does this by itself). */
 #define HP_STATUS_NONFINITE 1
 #define HP_STATUS_EXACT_ONLY 2
 int hp_net_status(hp_net* net, void* stream, int* flags);

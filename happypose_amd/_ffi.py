@@ -142,6 +142,19 @@ _PROTOS = {
     "hp_conv2d_nhwc": (C.c_int, [c_f32p, C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int,
                                  c_f32p, C.c_void_p]),
+    "hp_mv_estimate_camera_poses": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, c_i32p, C.c_int, c_f32p, c_f32p,
+                                              c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p]),
+    "hp_mv_score_matches": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_f32p, C.c_int, c_f32p, c_i32p, C.c_int, c_f32p, C.c_int,
+                                      c_f32p, C.c_int, c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_i32p,
+                                      C.c_void_p]),
+    "hp_mv_score_seed_matches": (C.c_int, [C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, c_f32p, c_i32p, C.c_int,
+                                           c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p]),
+    "hp_mv_ba_linearize": (C.c_int, [C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_i32p, c_i32p, c_f32p, c_f32p, c_f32p, C.c_int,
+                                     C.c_double, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "hp_ransac_make_infos": (C.c_int, [C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                       c_i32p, C.c_int64, c_i32p, C.c_int64]),
+    "hp_ransac_find_inliers": (C.c_int, [C.c_int64, c_i32p, c_i32p, C.c_int64, c_i32p, c_i32p, c_i32p, c_f32p, C.c_float, C.c_int,
+                                         c_i32p, c_i32p, C.POINTER(C.c_int64), c_i32p, C.POINTER(C.c_int64)]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -118,12 +118,13 @@ def sample_point_ids(n_pad: int, n_points: int) -> np.ndarray:
 
 class Meshes:
     """``TB/lib3d/rigid_mesh_database.py:151-169`` (tensor-collection of selected
-    objects).  ``points`` is ``[b, N_pad, 3]``."""
+    objects).  ``points`` is ``[b, N_pad, 3]``, ``symmetries`` ``[b, S_max, 4, 4]`` (or None)."""
 
-    def __init__(self, infos, labels, points):
+    def __init__(self, infos, labels, points, symmetries=None):
         self.infos = infos
         self.labels = np.asarray(labels)
         self.points = points
+        self.symmetries = symmetries
 
     def sample_points(self, n_points: int, deterministic: bool = False):
         n_pad = self.points.shape[1]
@@ -138,15 +139,44 @@ class BatchedMeshes:
     float32, metres.  ``points`` is a numpy array on the host and, after
     :meth:`to`, a torch tensor on the compute device."""
 
-    def __init__(self, infos, labels, points):
+    def __init__(self, infos, labels, points, symmetries=None, unsupported_symmetries=()):
         self.infos = infos
+        # labels whose symmetries could not be tabulated: the multi-view path refuses them (ops._mv_tables)
+        self.unsupported_symmetries = list(unsupported_symmetries)
         self.label_to_id: Dict[str, int] = {label: n for n, label in enumerate(labels)}
         self.labels = np.asarray(labels)
         self.points = points
+        # [n_obj, S_max, 4, 4] float32, rows past an object's own count are identity (CP/lib3d/rigid_mesh_database.py:73-77)
+        self.symmetries = symmetries
+        self._n_sym_device = None
+
+    @property
+    def device_tables(self):
+        """What the multi-view kernels read (csrc/multiview.hip): float32 views of ``points`` / ``symmetries`` as they are NOW
+        (after ``to`` / ``float`` / ``half`` there is one copy, not two) and the per-object ``n_sym``.  None before ``to()``."""
+        if self.symmetries is None or isinstance(self.points, np.ndarray):
+            return None
+        import torch
+
+        if self._n_sym_device is None or self._n_sym_device.device != self.points.device:
+            self._n_sym_device = torch.as_tensor(self.n_sym).to(self.points.device)
+        return {"points": self.points.to(torch.float32).contiguous(), "symmetries": self.symmetries.to(torch.float32).contiguous(),
+                "n_sym": self._n_sym_device}
+
+    @property
+    def n_sym_mapping(self) -> Dict[str, int]:
+        """``CP/lib3d/rigid_mesh_database.py:90-92``."""
+        return {label: obj["n_sym"] for label, obj in self.infos.items()}
+
+    @property
+    def n_sym(self) -> np.ndarray:
+        """Per-object symmetry count ``[n_obj]`` int32, in table order."""
+        return np.asarray([self.infos[label]["n_sym"] for label in self.labels], dtype=np.int32)
 
     def select(self, labels) -> Meshes:
         ids = [self.label_to_id[label] for label in labels]
-        return Meshes([self.infos[label] for label in labels], self.labels[ids], self.points[ids])
+        sym = None if self.symmetries is None else self.symmetries[ids]
+        return Meshes([self.infos[label] for label in labels], self.labels[ids], self.points[ids], sym)
 
     def ids_of(self, labels) -> np.ndarray:
         return np.asarray([self.label_to_id[label] for label in labels], dtype=np.int32)
@@ -155,6 +185,8 @@ class BatchedMeshes:
         import torch
 
         self.points = torch.as_tensor(self.points).to(device)
+        if self.symmetries is not None:
+            self.symmetries = torch.as_tensor(self.symmetries).to(device)
         return self
 
     def float(self):
@@ -182,16 +214,84 @@ class MeshDataBase:
     def from_object_ds(object_ds: RigidObjectDataset) -> "MeshDataBase":
         return MeshDataBase([object_ds[n] for n in range(len(object_ds))])
 
-    def batched(self) -> BatchedMeshes:
-        labels, points = [], []
+    def batched(self, aabb: bool = False, resample_n_points: Optional[int] = None, n_sym: int = 64) -> BatchedMeshes:
+        """``CP/lib3d/rigid_mesh_database.py:27-78``.  ``aabb=True``: the points are the 8 corners of the bounding
+        box; ``n_sym``: rotations per continuous symmetry axis.  The no-argument call gives the same points as
+        before; the symmetry table is always attached."""
+        if aabb:
+            assert resample_n_points is None
+        if resample_n_points:
+            raise NotImplementedError("resample_n_points needs trimesh's surface sampling, which is not a dependency")
+        labels, points, symmetries, unsupported = [], [], [], []
         new_infos = deepcopy(self.infos)
         for label, mesh in self.meshes.items():
-            pts = np.asarray(mesh.vertices, dtype=np.float64) * self.obj_dict[label].scale
+            obj = self.obj_dict[label]
+            pts = np.asarray(mesh.vertices, dtype=np.float64)
+            if aabb:
+                pts = bounding_box_corners(pts)
+            pts = pts * obj.scale
+            try:
+                sym = make_bop_symmetries(obj.symmetries_discrete, obj.symmetries_continuous, n_sym,
+                                          obj.scaling_factor_mesh_units_to_meters)
+            except UnsupportedSymmetryError:
+                # a continuous symmetry the reference's formula does not cover (offset, non-unit or negative axis): the
+                # single-view path never needed the table, so batching still works; the multi-view path says why it cannot
+                sym, unsupported = np.eye(4)[None], unsupported + [label]
             new_infos[label]["n_points"] = pts.shape[0]
+            new_infos[label]["n_sym"] = sym.shape[0]
             points.append(pts)
+            symmetries.append(sym)
             labels.append(label)
         pts = pad_stack_points(points).astype(np.float32)
-        return BatchedMeshes(new_infos, np.array(labels), pts)
+        s_max = max(len(s) for s in symmetries)
+        sym = np.tile(np.eye(4), (len(symmetries), s_max, 1, 1))
+        for n, s in enumerate(symmetries):
+            sym[n, :len(s)] = s
+        return BatchedMeshes(new_infos, np.array(labels), pts, sym.astype(np.float32), unsupported_symmetries=unsupported)
+
+
+def bounding_box_corners(pts: np.ndarray) -> np.ndarray:
+    """The 8 corners of the axis-aligned box of ``pts [n, 3]`` in the order of ``get_meshes_bounding_boxes``
+    (``CP/lib3d/mesh_ops.py:15-37``)."""
+    (x0, y0, z0), (x1, y1, z1) = pts.min(0), pts.max(0)
+    return np.array([[x0, y1, z1], [x1, y1, z1], [x1, y0, z1], [x0, y0, z1],
+                     [x0, y1, z0], [x1, y1, z0], [x1, y0, z0], [x0, y0, z0]], dtype=pts.dtype)
+
+
+class UnsupportedSymmetryError(ValueError):
+    """A continuous symmetry outside what ``make_bop_symmetries`` covers (offset, or an axis other than +x / +y / +z)."""
+
+
+def make_bop_symmetries(symmetries_discrete, symmetries_continuous, n_symmetries_continuous: int = 64,
+                        scale: float = 0.001) -> np.ndarray:
+    """Symmetry table of one object ``[S, 4, 4]`` float64, after ``make_bop_symmetries``
+    (``CP/lib3d/symmetries.py:7-35``): identity plus the discrete transforms (translation times ``scale``), each
+    composed on the left with ``n_symmetries_continuous`` rotations about every continuous axis (``sym_c * sym_d``,
+    continuous index fastest).  The rotation is ``euler2quat(axis * angle)`` in the ``sxyz`` convention, i.e.
+    ``Rz(a_z) @ Ry(a_y) @ Rx(a_x)``.  **Parity unpinned**: the reference builds these through pinocchio and
+    transforms3d, which are absent here; the table is restated from the formula."""
+    discrete = [np.eye(4)]
+    for sym_n in symmetries_discrete:
+        M = np.array(sym_n, dtype=np.float64).reshape(4, 4).copy()
+        M[:3, 3] *= scale
+        discrete.append(M)
+    continuous = []
+    for sym_n in symmetries_continuous:
+        axis = np.array(sym_n["axis"], dtype=np.float64)
+        if not np.allclose(sym_n["offset"], 0) or axis.sum() != 1:  # the reference asserts both (CP/lib3d/symmetries.py:20-22)
+            raise UnsupportedSymmetryError(f"continuous symmetry with axis {sym_n['axis']} and offset {sym_n['offset']}")
+        for n in range(n_symmetries_continuous):
+            ax, ay, az = axis * 2 * np.pi * n / n_symmetries_continuous
+            cx, sx, cy, sy, cz, sz = np.cos(ax), np.sin(ax), np.cos(ay), np.sin(ay), np.cos(az), np.sin(az)
+            Rx = np.array([[1.0, 0.0, 0.0], [0.0, cx, -sx], [0.0, sx, cx]])
+            Ry = np.array([[cy, 0.0, sy], [0.0, 1.0, 0.0], [-sy, 0.0, cy]])
+            Rz = np.array([[cz, -sz, 0.0], [sz, cz, 0.0], [0.0, 0.0, 1.0]])
+            M = np.eye(4)
+            M[:3, :3] = Rz @ Ry @ Rx
+            continuous.append(M)
+    if continuous:
+        return np.array([sym_c @ sym_d for sym_d in discrete for sym_c in continuous])
+    return np.array(discrete)
 
 
 def mip_chain(tex: np.ndarray):

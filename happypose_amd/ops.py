@@ -877,3 +877,178 @@ def conv2d_nhwc_f16(x, w_packed, stride, pad, bias=None, residual=None, pre_scal
                                        ptr(residual), ptr(pre_scale), ptr(pre_shift), int(relu), ptr(y),
                                        stream_ptr(dev)), "hp_conv2d_nhwc_f16")
     return y
+
+
+# ---- multi-view candidate matching (csrc/multiview.hip) ------------------------------------------------------------------------
+MV_DIST_3D, MV_DIST_REPROJECTED = 0, 1  # HP_MV_DIST_*
+_SEED_COLUMNS = ("view1", "view2", "match1_cand1", "match1_cand2", "match2_cand1", "match2_cand2")
+_MATCH_COLUMNS = ("hypothesis_id", "cand1", "cand2")
+
+
+def _h_i32(a) -> np.ndarray:
+    return np.ascontiguousarray(np.asarray(a), dtype=np.int32)
+
+
+def ransac_make_infos(view_ids, label_ids, n_ransac_iter: int, seed: int = 0):
+    """``cosypose_cext.make_ransac_infos`` (host): ``(seeds, tmatches)`` dicts of int32 arrays.  ``label_ids``: equal
+    integers for equal labels."""
+    view_ids, label_ids = _h_i32(view_ids), _h_i32(label_ids)
+    assert view_ids.shape == label_ids.shape and view_ids.ndim == 1
+    n = len(view_ids)
+    ns, nm = C.c_int64(0), C.c_int64(0)
+    check(lib().hp_ransac_make_infos(n, _np_ptr(view_ids), _np_ptr(label_ids), int(n_ransac_iter), int(seed), C.byref(ns),
+                                     C.byref(nm), None, 0, None, 0), "hp_ransac_make_infos")
+    seeds, matches = np.zeros((6, max(ns.value, 1)), np.int32), np.zeros((3, max(nm.value, 1)), np.int32)
+    check(lib().hp_ransac_make_infos(n, _np_ptr(view_ids), _np_ptr(label_ids), int(n_ransac_iter), int(seed), C.byref(ns),
+                                     C.byref(nm), _np_ptr(seeds), seeds.shape[1], _np_ptr(matches), matches.shape[1]),
+          "hp_ransac_make_infos")
+    return ({k: seeds[i, :ns.value].copy() for i, k in enumerate(_SEED_COLUMNS)},
+            {k: matches[i, :nm.value].copy() for i, k in enumerate(_MATCH_COLUMNS)})
+
+
+def ransac_find_inliers(seeds_view1, seeds_view2, hypothesis_id, cand1, cand2, dists, dist_threshold: float,
+                        n_min_inliers: int):
+    """``cosypose_cext.find_ransac_inliers`` (host): dict of ``inlier_matches_cand1`` / ``inlier_matches_cand2`` /
+    ``best_hypotheses`` int32 arrays."""
+    v1, v2, hid, c1, c2 = (_h_i32(a) for a in (seeds_view1, seeds_view2, hypothesis_id, cand1, cand2))
+    dists = np.ascontiguousarray(np.asarray(dists), dtype=np.float32)
+    assert len(v1) == len(v2) and len(hid) == len(c1) == len(c2) == len(dists)
+    in1, in2, best = (np.zeros(max(len(hid), 1), np.int32), np.zeros(max(len(hid), 1), np.int32),
+                      np.zeros(max(len(v1), 1), np.int32))
+    ni, nb = C.c_int64(0), C.c_int64(0)
+    check(lib().hp_ransac_find_inliers(len(v1), _np_ptr(v1), _np_ptr(v2), len(hid), _np_ptr(hid), _np_ptr(c1), _np_ptr(c2),
+                                       _np_ptr(dists), float(dist_threshold), int(n_min_inliers), _np_ptr(in1), _np_ptr(in2),
+                                       C.byref(ni), _np_ptr(best), C.byref(nb)), "hp_ransac_find_inliers")
+    return {"inlier_matches_cand1": in1[:ni.value].copy(), "inlier_matches_cand2": in2[:ni.value].copy(),
+            "best_hypotheses": best[:nb.value].copy()}
+
+
+def _mv_tables(mesh_db):
+    """Device tables of a ``BatchedMeshes`` that went through ``.to(device)``: (points, symmetries, n_sym, n_obj, n_pts, s_max)."""
+    if getattr(mesh_db, "unsupported_symmetries", None):
+        raise ValueError("continuous symmetries with an offset or an axis other than +x / +y / +z are not supported "
+                         f"(make_bop_symmetries): {mesh_db.unsupported_symmetries}")
+    t = getattr(mesh_db, "device_tables", None)
+    if t is None:
+        raise ValueError("the multi-view kernels need MeshDataBase.batched(...).to(device): no device tables on this mesh_db")
+    pts, sym, n_sym = t["points"], t["symmetries"], t["n_sym"]
+    assert pts.dim() == 3 and pts.shape[2] == 3 and sym.shape[0] == pts.shape[0] and sym.shape[2:] == (4, 4)
+    assert n_sym.shape == (pts.shape[0],) and n_sym.dtype == torch.int32
+    return pts, sym, n_sym, pts.shape[0], pts.shape[1], sym.shape[1]
+
+
+def mv_estimate_camera_poses(poses: torch.Tensor, cand_obj, seeds, mesh_db) -> torch.Tensor:
+    """``estimate_camera_poses_batch`` (``CP/multiview/ransac.py:23-75``) in one launch: ``TC1C2 [n_seeds, 4, 4]``.
+    ``poses [n_cand, 4, 4]``, ``cand_obj [n_cand]`` = row of each candidate's label in ``mesh_db``, ``seeds`` = the four
+    ``match*_cand*`` index columns (dict)."""
+    pts, sym, n_sym, n_obj, n_pts, s_max = _mv_tables(mesh_db)
+    dev = pts.device
+    n_cand = poses.shape[0]
+    assert poses.shape == (n_cand, 4, 4) and len(cand_obj) == n_cand
+    _check_ids(cand_obj, n_obj, "mv_estimate_camera_poses: cand_obj")
+    cols = []
+    for k in _SEED_COLUMNS[2:]:
+        _check_ids(seeds[k], n_cand, f"mv_estimate_camera_poses: {k}")
+        cols.append(_i32(seeds[k], dev))
+    n = len(cols[0])
+    poses, cand_obj = _f32(poses, dev), _i32(cand_obj, dev)
+    out = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_mv_estimate_camera_poses(n, ptr(cols[0]), ptr(cols[1]), ptr(cols[2]), ptr(cols[3]), ptr(poses),
+                                                ptr(cand_obj), n_cand, ptr(pts), ptr(sym), ptr(n_sym), n_obj, n_pts, s_max,
+                                                ptr(out), stream_ptr(dev)), "hp_mv_estimate_camera_poses")
+    return out
+
+
+def mv_score_matches(hypothesis_id, cand1, cand2, TC1C2: torch.Tensor, poses1: torch.Tensor, obj1, poses2: torch.Tensor,
+                     mesh_db, K: Optional[torch.Tensor] = None, return_sym_ids: bool = False):
+    """``score_tmaches_batch`` (``CP/multiview/ransac.py:78-99``) in one launch over the rows ``(hypothesis_id, cand1,
+    cand2)``: the symmetric distance between ``poses1[cand1]`` and ``TC1C2[hypothesis_id] @ poses2[cand2]`` for the
+    object ``obj1[cand1]``.  With ``K [n_hyp, 3, 3]`` the reprojected distance (``symmetric_distance_reprojected``) is
+    computed instead."""
+    pts, sym, n_sym, n_obj, n_pts, s_max = _mv_tables(mesh_db)
+    dev = pts.device
+    n_hyp, n1, n2 = TC1C2.shape[0], poses1.shape[0], poses2.shape[0]
+    assert TC1C2.shape == (n_hyp, 4, 4) and poses1.shape == (n1, 4, 4) and poses2.shape == (n2, 4, 4) and len(obj1) == n1
+    assert len(hypothesis_id) == len(cand1) == len(cand2)
+    _check_ids(hypothesis_id, n_hyp, "mv_score_matches: hypothesis_id")
+    _check_ids(cand1, n1, "mv_score_matches: cand1")
+    _check_ids(cand2, n2, "mv_score_matches: cand2")
+    _check_ids(obj1, n_obj, "mv_score_matches: obj1")
+    hid, c1, c2, obj1 = (_i32(a, dev) for a in (hypothesis_id, cand1, cand2, obj1))
+    TC1C2, poses1, poses2 = _f32(TC1C2, dev), _f32(poses1, dev), _f32(poses2, dev)
+    mode = MV_DIST_3D
+    if K is not None:
+        assert K.shape == (n_hyp, 3, 3)
+        K, mode = _f32(K, dev), MV_DIST_REPROJECTED
+    n = len(hid)
+    dists = torch.empty(n, dtype=torch.float32, device=dev)
+    sym_ids = torch.empty(n, dtype=torch.int32, device=dev) if return_sym_ids else None
+    with torch.cuda.device(dev):
+        check(lib().hp_mv_score_matches(n, ptr(hid), ptr(c1), ptr(c2), ptr(TC1C2), n_hyp, ptr(poses1), ptr(obj1), n1, ptr(poses2),
+                                        n2, ptr(K), mode, ptr(pts), ptr(sym), ptr(n_sym), n_obj, n_pts, s_max, ptr(dists),
+                                        ptr(sym_ids), stream_ptr(dev)), "hp_mv_score_matches")
+    return (dists, sym_ids) if return_sym_ids else dists
+
+
+def mv_ba_linearize(TWO_9d: torch.Tensor, TCW_9d: torch.Tensor, cand_obj, cand_view, TCO_cand: torch.Tensor, K: torch.Tensor,
+                    obj_points: torch.Tensor, residuals_threshold: float):
+    """One linearisation of the bundle adjustment (``MultiviewRefinement.forward_jacobian``,
+    ``CP/multiview/bundle_adjustment.py:223-270``): ``(errors [n_cand, n_pts, 2], clipped [n_cand, n_pts, 2],
+    JtJ [n_cand, 18, 18], Jte [n_cand, 18])``, all float64 -- see ``hp_mv_ba_linearize``."""
+    dev = TWO_9d.device
+    n_obj, n_views, n_cand, n_pts = TWO_9d.shape[0], TCW_9d.shape[0], TCO_cand.shape[0], obj_points.shape[1]
+    assert TWO_9d.shape == (n_obj, 9) and TCW_9d.shape == (n_views, 9) and TCO_cand.shape == (n_cand, 4, 4)
+    assert K.shape == (n_views, 3, 3) and obj_points.shape == (n_obj, n_pts, 3) and len(cand_obj) == len(cand_view) == n_cand
+    _check_ids(cand_obj, n_obj, "mv_ba_linearize: cand_obj")
+    _check_ids(cand_view, n_views, "mv_ba_linearize: cand_view")
+    TWO_9d, TCW_9d = (t.to(device=dev, dtype=torch.float64).contiguous() for t in (TWO_9d, TCW_9d))
+    TCO_cand, K, obj_points = (_f32(t, dev) for t in (TCO_cand, K, obj_points))
+    cand_obj, cand_view = _i32(cand_obj, dev), _i32(cand_view, dev)
+    errors = torch.empty(n_cand, n_pts, 2, dtype=torch.float64, device=dev)
+    clipped = torch.empty_like(errors)
+    JtJ = torch.empty(n_cand, 18, 18, dtype=torch.float64, device=dev)
+    Jte = torch.empty(n_cand, 18, dtype=torch.float64, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_mv_ba_linearize(n_cand, ptr(TWO_9d), n_obj, ptr(TCW_9d), n_views, ptr(cand_obj), ptr(cand_view),
+                                       ptr(TCO_cand), ptr(K), ptr(obj_points), n_pts, float(residuals_threshold), ptr(errors),
+                                       ptr(clipped), ptr(JtJ), ptr(Jte), stream_ptr(dev)), "hp_mv_ba_linearize")
+    return errors, clipped, JtJ, Jte
+
+
+def seed_row_tables(seeds, tmatches):
+    """Compact form of the tentative-match rows of ``ransac_make_infos``: ``(row_offsets [n_seeds + 1], pair_offsets [n_seeds],
+    pair_cand1, pair_cand2)`` int32 on the host.  The rows of a seed are contiguous and are the match list of its view pair in
+    the pair's order, so the list is kept once per view pair."""
+    n_seeds = len(seeds["view1"])
+    hid = np.asarray(tmatches["hypothesis_id"])
+    row_off = np.searchsorted(hid, np.arange(n_seeds + 1)).astype(np.int32)
+    pair_key = np.asarray(seeds["view1"]).astype(np.int64) * (1 << 32) + np.asarray(seeds["view2"]).astype(np.int64)
+    first = np.flatnonzero(np.r_[True, pair_key[1:] != pair_key[:-1]]) if n_seeds else np.zeros(0, np.int64)
+    counts = row_off[first + 1] - row_off[first]
+    table_off = np.r_[0, np.cumsum(counts)].astype(np.int64)
+    pair_of_seed = np.cumsum(np.r_[True, pair_key[1:] != pair_key[:-1]]) - 1 if n_seeds else np.zeros(0, np.int64)
+    take = np.concatenate([np.arange(row_off[f], row_off[f + 1]) for f in first]) if n_seeds else np.zeros(0, np.int64)
+    return (row_off, table_off[pair_of_seed].astype(np.int32), _h_i32(np.asarray(tmatches["cand1"])[take]),
+            _h_i32(np.asarray(tmatches["cand2"])[take]))
+
+
+def mv_score_seed_matches(seeds, tmatches, TC1C2: torch.Tensor, poses: torch.Tensor, cand_obj, mesh_db) -> torch.Tensor:
+    """``score_tmaches_batch`` for the rows of ``ransac_make_infos`` without uploading them: the device holds the per-seed
+    offsets and each view pair's match list once (``seed_row_tables``); the only per-row device memory is the result."""
+    pts, sym, n_sym, n_obj, n_pts, s_max = _mv_tables(mesh_db)
+    dev = pts.device
+    n_rows, n_seeds, n_cand = len(tmatches["hypothesis_id"]), TC1C2.shape[0], poses.shape[0]
+    assert TC1C2.shape == (n_seeds, 4, 4) and poses.shape == (n_cand, 4, 4) and len(cand_obj) == n_cand == len(poses)
+    assert len(seeds["view1"]) == n_seeds
+    _check_ids(cand_obj, n_obj, "mv_score_seed_matches: cand_obj")
+    _check_ids(tmatches["cand1"], n_cand, "mv_score_seed_matches: cand1")
+    _check_ids(tmatches["cand2"], n_cand, "mv_score_seed_matches: cand2")
+    row_off, pair_off, pc1, pc2 = (torch.as_tensor(a).to(dev) for a in seed_row_tables(seeds, tmatches))
+    TC1C2, poses, cand_obj = _f32(TC1C2, dev), _f32(poses, dev), _i32(cand_obj, dev)
+    dists = torch.empty(n_rows, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_mv_score_seed_matches(n_rows, n_seeds, ptr(row_off), ptr(pair_off), ptr(pc1), ptr(pc2), len(pc1), ptr(TC1C2),
+                                             ptr(poses), ptr(cand_obj), n_cand, ptr(pts), ptr(sym), ptr(n_sym), n_obj, n_pts, s_max,
+                                             ptr(dists), stream_ptr(dev)), "hp_mv_score_seed_matches")
+    return dists

@@ -180,3 +180,92 @@ def predictor_weights(shapes: Dict[str, Tuple[int, ...]], seed: int = 0,
         ident = np.array([1, 0, 0, 0, 1, 0, 0, 0, 1], np.float32)
         w["pose_fc.bias"] = ident[: len(w["pose_fc.bias"])].copy()
     return w
+
+
+def _look_at(eye: np.ndarray, up=(0.0, 0.0, 1.0)) -> np.ndarray:
+    """TWC of an OpenCV camera (z forward, y down) at ``eye`` looking at the origin."""
+    z = -eye / np.linalg.norm(eye)
+    x = np.cross(z, np.asarray(up))
+    x /= np.linalg.norm(x)
+    T = np.eye(4)
+    T[:3, :3] = np.stack([x, np.cross(z, x), z], axis=1)
+    T[:3, 3] = eye
+    return T
+
+
+MULTIVIEW_SCENES = {
+    # name: (n_ransac_iter, known camera poses); A: every seed pair enumerated (6 * 5 = 30 per view pair), B: fewer iterations
+    # than seed pairs (the two permutations decide), C: symmetric objects, two instances of a label, false candidates and a view
+    # that shares only two objects with the others, D: A with given cameras
+    "A": (30, False), "B": (12, False), "C": (2000, False), "D": (30, True),
+}
+
+
+def make_multiview_objects(seed: int = 11) -> RigidObjectDataset:
+    """Six small objects for the multi-view scenes: ``mv_0`` has a 2-fold discrete symmetry (half a turn about z), ``mv_1`` a
+    continuous symmetry axis z, the others none."""
+    rs = np.random.RandomState(seed)
+    objs = []
+    for i in range(6):
+        mesh = make_mesh(seed * 1000 + i, n_lat=8, n_lon=12, diameter=float(rs.uniform(0.10, 0.25)), tex_size=16)
+        kw = {}
+        if i == 0:
+            kw["symmetries_discrete"] = [np.diag([-1.0, -1.0, 1.0, 1.0]).reshape(-1).tolist()]
+        if i == 1:
+            kw["symmetries_continuous"] = [{"axis": [0, 0, 1], "offset": [0, 0, 0]}]
+        objs.append(RigidObject(label=f"mv_{i}", mesh_path=mesh, mesh_units="m", **kw))
+    return RigidObjectDataset(objs)
+
+
+def make_multiview_scene(name: str, seed: int = 5, n_views: int = 4, n_objects: int = 6, n_false: int = 0):
+    """Seeded synthetic multi-view scene: ground-truth ``TWO`` / ``TWC`` and per-view candidates ``TCO = inv(TWC) TWO`` with
+    pose noise (about 0.1 deg, 1 mm: symmetric distances of a few mm, far below the matching threshold of 0.02) -- false
+    candidates are displaced by 0.1 - 0.3 m (far above it).  ``name``: a key of ``MULTIVIEW_SCENES`` ("A", "B" and "D" are the
+    same candidates) or "scale" (``n_views`` / ``n_objects`` / ``n_false`` free).  Returns a dict of arrays: ``view_id``,
+    ``label_id`` (index into ``make_multiview_objects``), ``score``, ``poses`` float32, ``TWC``, ``K``, ``TWO``,
+    ``gt_obj`` (-1: false candidate).  The false candidates carry labels without symmetries: two candidates of one SYMMETRIC
+    label in a view make seeds whose symmetry choice is an exact tie in real arithmetic (``dist(G S, A S) == dist(G, A)``), which
+    rounding alone decides -- in the reference as much as here -- so no test could pin it."""
+    rs = np.random.RandomState(seed)
+    scene_c = name == "C"
+    if name != "scale":
+        n_views, n_objects = 4, 6
+    obj_label = np.arange(n_objects) % 6
+    if scene_c:
+        obj_label = np.array([0, 1, 2, 2, 3, 4])  # two instances of mv_2
+    TWO = np.tile(np.eye(4), (n_objects, 1, 1))
+    TWO[:, :3, :3] = random_rotations(rs, n_objects)
+    TWO[:, :3, 3] = rs.uniform(-0.3, 0.3, (n_objects, 3)) * (1.0 + 0.25 * (n_objects > 8))
+    az = np.linspace(0.0, 2 * np.pi, n_views, endpoint=False) + rs.uniform(-0.2, 0.2, n_views)
+    el = rs.uniform(0.4, 0.9, n_views)
+    TWC = np.stack([_look_at(1.2 * np.array([np.cos(a) * np.cos(e), np.sin(a) * np.cos(e), np.sin(e)])) for a, e in zip(az, el)])
+    K = np.tile(np.array([[600.0, 0.0, 320.0], [0.0, 600.0, 240.0], [0.0, 0.0, 1.0]]), (n_views, 1, 1))
+    rows = []
+    for v in range(n_views):
+        TCW = np.linalg.inv(TWC[v])
+        visible = range(n_objects)
+        if scene_c and v == 3:
+            visible = [4, 5]  # fewer than n_min_inliers = 3 shared objects: this view cannot join the others
+        for o in visible:
+            N = np.eye(4)
+            N[:3, :3] = euler_to_R(rs.normal(0.0, np.deg2rad(0.1), 3))[0]
+            N[:3, 3] = rs.normal(0.0, 0.001, 3)
+            T = TCW @ TWO[o] @ N
+            if scene_c and obj_label[o] == 0 and rs.rand() < 0.5:
+                T = T @ np.diag([-1.0, -1.0, 1.0, 1.0])  # the detector may answer either of the two equivalent poses
+            if scene_c and obj_label[o] == 1:
+                a = rs.uniform(0, 2 * np.pi)  # ... or any turn about the axis
+                Rz = np.eye(4)
+                Rz[:2, :2] = [[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]]
+                T = T @ Rz
+            rows.append((v, obj_label[o], rs.uniform(0.6, 1.0), T, o))
+        false = [(3, 0.9), (2, 0.8), (5, 0.1)] if scene_c else [(int(rs.randint(6)), 0.7)] * n_false
+        for lab, score in (false if (scene_c or name == "scale") else []):
+            T = TCW @ TWO[int(rs.randint(n_objects))]
+            T[:3, :3] = T[:3, :3] @ random_rotations(rs, 1)[0]
+            d = rs.normal(size=3)
+            T[:3, 3] += d / np.linalg.norm(d) * rs.uniform(0.1, 0.3)
+            rows.append((v, lab, score, T, -1))
+    return {"view_id": np.array([r[0] for r in rows], np.int64), "label_id": np.array([r[1] for r in rows], np.int64),
+            "score": np.array([r[2] for r in rows]), "poses": np.stack([r[3] for r in rows]).astype(np.float32),
+            "gt_obj": np.array([r[4] for r in rows], np.int64), "TWC": TWC, "K": K, "TWO": TWO}

@@ -621,6 +621,85 @@ int hp_conv2d_nhwc_f16(const void* d_x, int n, int h, int w, int cin, const void
                        const void* d_pre_scale, const void* d_pre_shift, int relu, void* d_y,
                        void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Multi-view scene reconstruction: the candidate matching of "consistent multi-view multi-object pose estimation"
+ * (CP/multiview/ransac.py, CP/lib3d/symmetric_distances.py, CP/csrc/cosypose_cext.cpp).  csrc/multiview.hip.
+ *
+ * Mesh tables (MeshDataBase.batched(aabb=..., n_sym=...).to(device), CP/lib3d/rigid_mesh_database.py:27-78):
+ * d_points [n_obj][n_pts][3] metres, d_symmetries [n_obj][s_max][16] (rows past an object's count are identity),
+ * d_n_sym [n_obj] with 1 <= n_sym <= s_max.  Poses are [.][16].  Index columns are int32 on the device; an index
+ * outside its table (or an n_sym outside 1..s_max) gives NaN in that row's output and reads nothing outside the tables.
+ * One wavefront per row: results do not depend on launch geometry, no [rows][s_max] temporary exists.
+ * ---------------------------------------------------------------------------------- */
+#define HP_MV_DIST_3D 0
+#define HP_MV_DIST_REPROJECTED 1
+/* estimate_camera_poses (CP/multiview/ransac.py:23-50), one launch over all seeds.  For seed n with a = match1_cand1[n],
+ * b = match1_cand2[n], g = match2_cand1[n], d = match2_cand2[n]: over the n_sym symmetries S of a's object, the distance of
+ * symmetric_distance_batched_fast (below, itself minimised over the symmetries of g's object, on g's points) between
+ * poses[g] and poses[a] S inv(poses[b]) poses[d]; the first strict minimum S* in symmetry order (scatter_argmin,
+ * CP/csrc/cosypose_cext.cpp:220-247) gives d_TC1C2[n] = poses[a] S* inv(poses[b]). */
+int hp_mv_estimate_camera_poses(int n_seeds, const int32_t* d_match1_cand1, const int32_t* d_match1_cand2,
+                                const int32_t* d_match2_cand1, const int32_t* d_match2_cand2, const float* d_poses,
+                                const int32_t* d_cand_obj, int n_cand, const float* d_points, const float* d_symmetries,
+                                const int32_t* d_n_sym, int n_obj, int n_pts, int s_max, float* d_TC1C2, void* stream);
+/* score_tmaches_batch / score_tmatches (CP/multiview/ransac.py:78-99), one launch over the tentative-match rows, gathered by
+ * index on the device.  Row r: T1 = poses1[cand1[r]], T2 = TC1C2[hypothesis_id[r]] poses2[cand2[r]], object
+ * obj1[cand1[r]].  (The matching passes the candidate table as poses1 and poses2.)
+ *  HP_MV_DIST_3D: symmetric_distance_batched_fast (CP/lib3d/symmetric_distances.py:36-55): the symmetry S with the smallest
+ *    MEAN OF SQUARED distances between (T1 S) p and T2 p over the object's points, lowest index on a tie; d_dists[r] is the
+ *    MEAN OF THE ROOTS for that S.
+ *  HP_MV_DIST_REPROJECTED: symmetric_distance_reprojected (:103-122) with d_K [n_hyp][9] indexed by hypothesis_id: the
+ *    smallest mean L2 pixel distance of project_points (CP/lib3d/camera_geometry.py:4-18), first strict minimum.
+ * d_sym_ids [n_rows] (may be NULL) receives the index of the chosen symmetry (-1 for a guarded row). */
+int hp_mv_score_matches(int n_rows, const int32_t* d_hypothesis_id, const int32_t* d_cand1, const int32_t* d_cand2,
+                        const float* d_TC1C2, int n_hyp, const float* d_poses1, const int32_t* d_obj1, int n_cand1,
+                        const float* d_poses2, int n_cand2, const float* d_K, int mode, const float* d_points,
+                        const float* d_symmetries, const int32_t* d_n_sym, int n_obj, int n_pts, int s_max, float* d_dists,
+                        int32_t* d_sym_ids, void* stream);
+/* The same 3D score for the rows of the candidate matching WITHOUT per-row index columns: every seed of a view pair lists all
+ * tentative matches of that pair (make_ransac_infos), so the rows of seed n are d_row_offsets[n] .. d_row_offsets[n + 1]
+ * ([n_seeds + 1], ascending from 0 to n_rows) and row r of them is match d_pair_offsets[n] + r - d_row_offsets[n] of the pair
+ * tables d_pair_cand1 / d_pair_cand2 [n_pair_matches] (the tentative matches of each view pair once).  The only per-row device
+ * memory is d_dists [n_rows].  A row outside the offsets or a match outside the pair tables gives NaN. */
+int hp_mv_score_seed_matches(int n_rows, int n_seeds, const int32_t* d_row_offsets, const int32_t* d_pair_offsets,
+                             const int32_t* d_pair_cand1, const int32_t* d_pair_cand2, int n_pair_matches, const float* d_TC1C2,
+                             const float* d_poses, const int32_t* d_cand_obj, int n_cand, const float* d_points,
+                             const float* d_symmetries, const int32_t* d_n_sym, int n_obj, int n_pts, int s_max, float* d_dists,
+                             void* stream);
+/* Body of MultiviewRefinement.forward_jacobian (CP/multiview/bundle_adjustment.py:223-270) without autograd, one wavefront per
+ * candidate c with object o = cand_obj[c] and view v = cand_view[c]:  yhat = project(K[v], T(TCW_9d[v]) T(TWO_9d[o]) p),
+ * y = project(K[v], TCO_cand[c] p) over the n_pts points of d_obj_points [n_obj][n_pts][3]; T(.) is
+ * compute_transform_from_pose9d (CP/lib3d/transform_ops.py:57, Gram-Schmidt of TB/lib3d/rotations.py:22), differentiated
+ * analytically (forward mode).  Outputs: d_errors [n_cand][n_pts][2] = y - yhat (UNCLIPPED: what the LM step uses),
+ * d_clipped [n_cand][n_pts][2] = min(errors^2, residuals_threshold) (its mean is the loss), d_JtJ [n_cand][18][18] and
+ * d_Jte [n_cand][18] = J^T J and J^T errors of the candidate, J = d yhat / d (9 object, 9 view parameters), summed over the points
+ * in table order.  The caller adds the blocks into the full matrix in candidate order.  TCO_cand is the candidate's pose already
+ * aligned by its symmetry (hp_mv_score_matches, HP_MV_DIST_REPROJECTED).  An o / v outside its table gives NaN outputs.
+ * The parameters and the four outputs are DOUBLE (the host solves the normal equations in float64 and float32 blocks change the
+ * LM run's accept / reject path on ill-conditioned scenes); candidate poses, K and points are the float32 tables. */
+int hp_mv_ba_linearize(int n_cand, const double* d_TWO_9d, int n_obj, const double* d_TCW_9d, int n_views, const int32_t* d_cand_obj,
+                       const int32_t* d_cand_view, const float* d_TCO_cand, const float* d_K, const float* d_obj_points, int n_pts,
+                       double residuals_threshold, double* d_errors, double* d_clipped, double* d_JtJ, double* d_Jte, void* stream);
+/* Host only (no device work).  make_ransac_infos (CP/csrc/cosypose_cext.cpp:38-107): tentative matches are the ordered pairs
+ * (n, m) of candidates in different views with equal label ids; the view pairs are walked in ascending (view1, view2) order,
+ * each with two permutations of its matches -- std::shuffle with std::default_random_engine(seed) and (seed + 1) -- and at
+ * most n_ransac_iter seeds (pairs of distinct matches) per view pair; every seed lists all tentative matches of its view pair.
+ * h_seeds [6][cap_seeds] = view1, view2, match1_cand1, match1_cand2, match2_cand1, match2_cand2; h_matches [3][cap_matches] =
+ * hypothesis_id, cand1, cand2.  Call with both tables NULL to get the sizes, then with tables of at least those capacities. */
+int hp_ransac_make_infos(int n_cand, const int32_t* h_view_ids, const int32_t* h_label_ids, int n_ransac_iter, int seed,
+                         int64_t* n_seeds, int64_t* n_matches, int32_t* h_seeds, int64_t cap_seeds, int32_t* h_matches,
+                         int64_t cap_matches);
+/* find_ransac_inliers (CP/csrc/cosypose_cext.cpp:109-218).  Inliers of a hypothesis: matches with dist <= dist_threshold, made
+ * one-to-one greedily by ascending distance (stable).  Per view pair (ascending order) the hypothesis with at least
+ * n_min_inliers inliers wins that has more inliers, then the strictly smaller distance sum.  As in the reference a view pair is
+ * kept only if the winning hypothesis id is > 0: hypothesis 0 -- the first seed of the first view pair -- can never be
+ * selected.  That quirk is reproduced on purpose.  h_inlier_cand1 / h_inlier_cand2 hold up to n_matches entries,
+ * h_best_hypotheses up to n_hyp. */
+int hp_ransac_find_inliers(int64_t n_hyp, const int32_t* h_view1, const int32_t* h_view2, int64_t n_matches,
+                           const int32_t* h_hypothesis_id, const int32_t* h_cand1, const int32_t* h_cand2, const float* h_dists,
+                           float dist_threshold, int n_min_inliers, int32_t* h_inlier_cand1, int32_t* h_inlier_cand2,
+                           int64_t* n_inliers, int32_t* h_best_hypotheses, int64_t* n_best);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

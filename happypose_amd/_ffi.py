@@ -155,6 +155,10 @@ _PROTOS = {
                                        c_i32p, C.c_int64, c_i32p, C.c_int64]),
     "hp_ransac_find_inliers": (C.c_int, [C.c_int64, c_i32p, c_i32p, C.c_int64, c_i32p, c_i32p, c_i32p, c_f32p, C.c_float, C.c_int,
                                          c_i32p, c_i32p, C.POINTER(C.c_int64), c_i32p, C.POINTER(C.c_int64)]),
+    "hp_pose_errors_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "hp_pose_errors": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p,
+                                 c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_i32p,
+                                 C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

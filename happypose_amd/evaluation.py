@@ -1,0 +1,458 @@
+"""Pose-error metrics and the pose-error meter of the evaluation, on the device.
+
+Drop-in for ``TB/lib3d/distances.py`` (``dists_add``, ``dists_add_symmetric``, ``dists_add_symmetries``),
+``CP/lib3d/symmetric_distances.py::chamfer_dist`` and ``CP/evaluation/meters/pose_meters.py::PoseErrorMeter`` with the helpers of
+``CP/evaluation/meters/utils.py``; ``mssd`` / ``mspd`` are BOP's two further pose errors, which the reference leaves to
+``bop_toolkit``.  All errors come from ONE kernel family (``ops.pose_errors``, ``csrc/pose_errors.hip``): the nearest-neighbour
+search of ADD-S is tiled, so nothing of size ``P x P`` is ever allocated and a whole evaluation batch is one launch.
+
+Differences from the reference, all on the host side:
+  * no xarray: ``PoseErrorMeter.summary()`` returns ``gt`` / ``matches`` / ``preds`` / ``ap`` as pandas DataFrames with the
+    reference's variable names as columns; the array-valued variables (``xyz``, ``TCO_xyz``, ``TXO_pred``) are object columns
+    holding one numpy array per row, and the per-object AUC table is ``gt.attrs["AUC/objects"]``;
+  * no scikit-learn: the average precision is :func:`average_precision`;
+  * ``errors_bsz`` is accepted and ignored: it bounded the reference's ``[b, P, P, 3]`` temporary, and there is none to bound --
+    ``exact_meshes=True`` therefore no longer needs ``errors_bsz == 1``.
+"""
+
+from __future__ import annotations
+
+from collections import OrderedDict, defaultdict
+from typing import Dict, Optional, Sequence
+
+import numpy as np
+import pandas as pd
+import torch
+
+from . import ops
+
+GROUP_KEYS = ("scene_id", "view_id", "label")
+ERROR_TYPES = ("ADD", "ADD-S", "ADD(-S)", "ADD-SYM", "MSSD", "MSPD")
+_MAX_ERRORS = ("MSSD", "MSPD")  # the metric is the largest per-point distance, not the mean
+
+
+# ---- distances on explicit point sets (TB/lib3d/distances.py) --------------------------------------------------------------------
+def _transform_pts(T: torch.Tensor, pts: torch.Tensor) -> torch.Tensor:
+    out = pts @ T[..., :3, :3].transpose(-1, -2)
+    out += T[..., None, :3, 3]
+    return out
+
+
+def _rows_on_points(mode: str, TXO_pred, TXO_gt, points, symmetries=None, **kw):
+    """One row per batch entry, each with its own point set (and symmetry set): the tables have one 'object' per row."""
+    b, n_pts = points.shape[0], points.shape[1]
+    dev = points.device
+    if symmetries is None:
+        symmetries = torch.eye(4, dtype=torch.float32, device=dev).expand(b, 1, 4, 4)
+    ids = torch.arange(b, dtype=torch.int32)
+    return ops.pose_errors_tables(ids, ids, ids, np.full(b, ops.POSE_ERR_MODES[mode], np.int32), TXO_pred, TXO_gt, points, symmetries,
+                                  torch.full((b,), symmetries.shape[1], dtype=torch.int32, device=dev),
+                                  torch.full((b,), n_pts, dtype=torch.int32, device=dev), **kw)
+
+
+def dists_add(TXO_pred: torch.Tensor, TXO_gt: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+    """``T_gt p - T_pred p`` for every point: ``[b, P, 3]``."""
+    return _transform_pts(TXO_gt, points) - _transform_pts(TXO_pred, points)
+
+
+def dists_add_symmetric(TXO_pred: torch.Tensor, TXO_gt: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+    """For every ground-truth point the difference to its nearest predicted point: ``[b, P, 3]``.  The neighbours come from the
+    tiled kernel (``assign``); the only temporaries are ``[b, P]`` and ``[b, P, 3]``."""
+    if points.shape[0] == 0:
+        return points.new_zeros(points.shape)
+    assign = _rows_on_points("ADD-S", TXO_pred, TXO_gt, points, return_assign=True)["assign"].long()
+    picked = torch.gather(_transform_pts(TXO_pred, points), 1, assign.unsqueeze(-1).expand(-1, -1, 3))
+    dists = _transform_pts(TXO_gt, points)
+    dists -= picked
+    return dists
+
+
+def dists_add_symmetries(TXO_pred: torch.Tensor, TXO_gt_possible: torch.Tensor, points: torch.Tensor) -> torch.Tensor:
+    """``TXO_gt_possible [b, S, 4, 4]``: the ground truth under each symmetry.  Differences for the one with the smallest mean
+    norm: ``[b, P, 3]``."""
+    b = TXO_pred.shape[0]
+    if b == 0:
+        return points.new_zeros(points.shape)
+    eye = torch.eye(4, dtype=torch.float32, device=points.device).expand(b, 4, 4)
+    sym_id = _rows_on_points("ADD-SYM", TXO_pred, eye, points, symmetries=TXO_gt_possible)["sym_id"].long()
+    TXO_gt = TXO_gt_possible[torch.arange(b, device=sym_id.device), sym_id]
+    return _transform_pts(TXO_gt, points) - _transform_pts(TXO_pred, points)
+
+
+# ---- distances on a mesh database ------------------------------------------------------------------------------------------------
+def _rows_on_meshes(mode: str, T_pred, T_gt, labels, mesh_db, K=None, exact_meshes=False):
+    ids = torch.arange(len(labels), dtype=torch.int32)
+    return ops.pose_errors(ids, ids, mesh_db.ids_of(labels), np.full(len(labels), ops.POSE_ERR_MODES[mode], np.int32), T_pred, T_gt,
+                           mesh_db, K=K, exact_meshes=exact_meshes)
+
+
+def chamfer_dist(T1: torch.Tensor, T2: torch.Tensor, labels, mesh_db):
+    """``(dists [b], None)``: mean distance from every point of the object under ``T1`` to the nearest point under ``T2``, over
+    the padded point table like the reference."""
+    bsz = T1.shape[0]
+    assert T1.shape == (bsz, 4, 4) and T2.shape == (bsz, 4, 4) and len(labels) == bsz
+    if bsz == 0:
+        return torch.empty(0, dtype=T1.dtype, device=T1.device), None
+    return _rows_on_meshes("ADD-S", T2, T1, labels, mesh_db)["norm_avg"], None
+
+
+def mssd(TXO_pred: torch.Tensor, TXO_gt: torch.Tensor, labels, mesh_db, exact_meshes: bool = True) -> torch.Tensor:
+    """Maximum symmetry-aware surface distance (BOP): ``min_S max_j |T_pred p_j - T_gt S p_j|``, ``[b]`` metres."""
+    return _rows_on_meshes("MSSD", TXO_pred, TXO_gt, labels, mesh_db, exact_meshes=exact_meshes)["norm_max"]
+
+
+def mspd(TXO_pred: torch.Tensor, TXO_gt: torch.Tensor, K: torch.Tensor, labels, mesh_db, exact_meshes: bool = True) -> torch.Tensor:
+    """Maximum symmetry-aware projection distance (BOP): as :func:`mssd` with both sides projected by ``K [b, 3, 3]``, pixels."""
+    return _rows_on_meshes("MSPD", TXO_pred, TXO_gt, labels, mesh_db, K=K, exact_meshes=exact_meshes)["norm_max"]
+
+
+# ---- bookkeeping of the meter (CP/evaluation/meters/utils.py) ---------------------------------------------------------------------
+def add_inst_num(infos: pd.DataFrame, group_keys=GROUP_KEYS, key: str = "pred_inst_num") -> pd.DataFrame:
+    """Number the rows of every group 0, 1, ... in row order (column ``key``, added in place)."""
+    infos[key] = infos.groupby(list(group_keys), sort=False).cumcount().to_numpy(dtype=int)
+    return infos
+
+
+def get_top_n_ids(infos: pd.DataFrame, group_keys=GROUP_KEYS, top_key: str = "score", n_top: int = -1, targets=None):
+    """Row positions of the best rows of every group by descending ``top_key``: ``n_top`` of them if positive, else the group's
+    ``inst_count`` in ``targets`` (0 for a group that is no target), else all.  Groups in sorted key order."""
+    keys = list(group_keys)
+    counts = None
+    if n_top <= 0 and targets is not None:
+        counts = {k: targets.loc[ids[0], "inst_count"] for k, ids in targets.groupby(keys).groups.items()}
+    position = pd.Series(np.arange(len(infos)), index=infos.index)
+    keep = []
+    for k, ids in infos.groupby(keys).groups.items():
+        ranked = infos.loc[ids].sort_values(top_key, ascending=False)
+        n = n_top if n_top > 0 else (counts.get(k, 0) if counts is not None else len(ranked))
+        keep.append(position.loc[ranked.index].to_numpy()[:n])
+    return np.concatenate(keep) if keep else []
+
+
+def add_valid_gt(gt_infos: pd.DataFrame, group_keys=GROUP_KEYS, visib_gt_min: float = -1, targets=None) -> pd.DataFrame:
+    """Column ``valid``: visible enough (``visib_fract >= visib_gt_min``, and a target label) when a minimum is given; else the
+    most visible ``inst_count`` instances of every target group; else everything."""
+    if visib_gt_min > 0:
+        valid = (gt_infos["visib_fract"] >= visib_gt_min).to_numpy()
+        if targets is not None:
+            valid = valid & np.isin(gt_infos["label"], targets["label"])
+        gt_infos["valid"] = valid
+    elif targets is not None:
+        valid = np.zeros(len(gt_infos), dtype=bool)
+        ids = get_top_n_ids(gt_infos, group_keys=group_keys, top_key="visib_fract", targets=targets)
+        valid[np.asarray(ids, dtype=int)] = True
+        gt_infos["valid"] = valid
+    else:
+        gt_infos["valid"] = True
+    return gt_infos
+
+
+def get_candidate_matches(pred_infos: pd.DataFrame, gt_infos: pd.DataFrame, group_keys=GROUP_KEYS, only_valids: bool = True):
+    """Every (prediction, ground truth) pair of one group: the inner join on the group keys with ``pred_id`` / ``gt_id`` (row
+    positions, added to both frames in place) and ``cand_id``."""
+    pred_infos["pred_id"] = np.arange(len(pred_infos))
+    gt_infos["gt_id"] = np.arange(len(gt_infos))
+    cands = pred_infos.merge(gt_infos, on=list(group_keys))
+    if only_valids:
+        cands = cands[cands["valid"]].reset_index(drop=True)
+    cands["cand_id"] = np.arange(len(cands))
+    return cands
+
+
+def match_poses(cand_infos: pd.DataFrame, group_keys=GROUP_KEYS) -> pd.DataFrame:
+    """Greedy one-to-one matching inside every group: predictions by descending score, each takes the still-free ground truth
+    with the smallest finite ``error`` (the first one on a tie)."""
+    assert "error" in cand_infos
+    if len(cand_infos) == 0:
+        return cand_infos
+    chosen = []
+    for _, group in cand_infos.groupby(list(group_keys)):
+        order = group.drop_duplicates("pred_id").sort_values("score", ascending=False)["pred_id"]
+        taken = set()
+        for pred_id in order:
+            free = group[(group["pred_id"] == pred_id) & ~group["gt_id"].isin(taken) & (group["error"] < np.inf)]
+            if len(free):
+                best = free["error"].idxmin()
+                taken.add(free.loc[best, "gt_id"])
+                chosen.append(best)
+    return cand_infos.loc[chosen].reset_index(drop=True)
+
+
+def compute_auc_posecnn(errors) -> float:
+    """Area under the accuracy-threshold curve up to 0.1 m, as the YCB-Video toolbox computes it (PoseCNN), scaled to 0..1."""
+    d = np.sort(np.array(errors, dtype=float))
+    accuracy = np.cumsum(np.ones(len(d))) / max(len(d), 1)
+    inside = np.isfinite(d) & ~(d > 0.1)
+    if not inside.any():
+        return np.nan
+    d, accuracy = d[inside], accuracy[inside]
+    mrec = np.concatenate(([0], d, [0.1]))
+    mpre = np.maximum.accumulate(np.concatenate(([0], accuracy, [accuracy[-1]])))
+    steps = np.where(mrec[1:] != mrec[:-1])[0] + 1
+    return ((mrec[steps] - mrec[steps - 1]) * mpre[steps]).sum() * 10
+
+
+def average_precision(y_true, y_score) -> float:
+    """``sum_n (R_n - R_{n-1}) P_n`` over the distinct score thresholds in descending order -- what
+    ``sklearn.metrics.average_precision_score`` computes for binary labels.  0 without a positive."""
+    y_true, y_score = np.asarray(y_true, dtype=float), np.asarray(y_score, dtype=float)
+    if y_true.sum() == 0:
+        return 0.0
+    order = np.argsort(-y_score, kind="mergesort")
+    y_true, y_score = y_true[order], y_score[order]
+    last_of_threshold = np.r_[np.where(np.diff(y_score))[0], len(y_score) - 1]
+    tps = np.cumsum(y_true)[last_of_threshold]
+    precision = tps / (last_of_threshold + 1)
+    recall = tps / tps[-1]
+    return float(np.sum(np.diff(np.r_[0.0, recall]) * precision))
+
+
+# ---- the meter -------------------------------------------------------------------------------------------------------------------
+_FILL = {"norm": np.inf, "0.1d": False, "xyz": np.inf, "TCO_xyz": np.inf, "TCO_norm": np.inf, "obj_diameter": np.nan,
+         "TXO_pred": np.nan, "score": np.nan}
+_ARRAY_COLUMNS = {"xyz": (3,), "TCO_xyz": (3,), "TXO_pred": (4, 4)}
+
+
+def _left_join(left: pd.DataFrame, right: pd.DataFrame, on: Sequence[str]) -> pd.DataFrame:
+    """The reference's ``xr_merge``: every column of ``right`` that is not a key is added to a copy of ``left``, taken from the
+    row of ``right`` with equal keys and filled per ``_FILL`` (NaN otherwise) where there is none.  One row per left row."""
+    on = list(on)
+    idx = left[on].merge(right[on].assign(_row=np.arange(len(right))), on=on, how="left")
+    assert len(idx) == len(left), "join keys are not unique"
+    src = idx["_row"].to_numpy(dtype=float)
+    have = np.isfinite(src)
+    src = src[have].astype(int)
+    out = left.copy()
+    for col in right.columns:
+        if col in on:
+            continue
+        fill = _FILL.get(col, np.nan)
+        if col in _ARRAY_COLUMNS:
+            values = _array_column([np.full(_ARRAY_COLUMNS[col], fill) for _ in range(len(left))])
+            taken = right[col].to_numpy()
+            for i, j in zip(np.where(have)[0], src):
+                values[i] = taken[j]
+        else:
+            values = np.full(len(left), fill, dtype=np.array(fill).dtype)
+            values[have] = right[col].to_numpy()[src]
+        out[col] = values
+    return out
+
+
+def _array_column(a) -> np.ndarray:
+    """Object column with one array per row (numpy would otherwise stack equal shapes into one array)."""
+    col = np.empty(len(a), dtype=object)
+    for i, v in enumerate(a):
+        col[i] = v
+    return col
+
+
+class PoseErrorMeter:
+    """The reference's meter with its constructor arguments.  ``error_type``: ``ADD``, ``ADD-S``, ``ADD(-S)`` (ADD-S for the
+    labels whose ``infos[label]["is_symmetric"]`` is true, ADD for the rest -- one launch), and beyond the reference ``ADD-SYM``,
+    ``MSSD`` and ``MSPD``.  MSPD reads ``gt_data.K [n, 3, 3]`` and, being in pixels, compares the error with ``match_threshold``
+    and the ``0.1d`` flag with ``match_threshold`` itself instead of a fraction of the diameter.
+
+    ``mesh_db``: a ``MeshDataBase`` (batched here) or its ``batched()`` tables.  ``errors_bsz`` is kept for compatibility and
+    does not bound memory any more: every candidate of an :meth:`add` call is scored in one ``ops.pose_errors`` launch."""
+
+    def __init__(self, mesh_db, error_type="ADD", report_AP=False, report_error_AUC=False, report_error_stats=False,
+                 sample_n_points=None, errors_bsz=1, match_threshold=0.1, exact_meshes=True, spheres_overlap_check=True,
+                 consider_all_predictions=False, targets=None, visib_gt_min=-1, n_top=-1, device="cuda"):
+        self.sample_n_points = sample_n_points
+        self.mesh_db = (mesh_db.batched() if hasattr(mesh_db, "batched") else mesh_db).to(device).float()
+        self.device = device
+        self.error_type = error_type.upper()
+        if self.error_type not in ERROR_TYPES:
+            raise ValueError("Error not supported", self.error_type)
+        self.errors_bsz = errors_bsz
+        self.n_top = n_top
+        self.exact_meshes = exact_meshes
+        self.visib_gt_min = visib_gt_min
+        self.targets = targets
+        self.match_threshold = match_threshold
+        self.spheres_overlap_check = spheres_overlap_check
+        self.consider_all_predictions = consider_all_predictions
+        self.report_AP = report_AP
+        self.report_error_stats = report_error_stats
+        self.report_error_AUC = report_error_AUC
+        self.reset()
+        if self.exact_meshes:
+            assert sample_n_points is None
+
+    def reset(self):
+        self.datas = defaultdict(list)
+
+    # -- errors --------------------------------------------------------------------------------------------------------------------
+    def _row_modes(self, labels) -> np.ndarray:
+        if self.error_type == "ADD(-S)":
+            names = ["ADD-S" if self.mesh_db.infos[label]["is_symmetric"] else "ADD" for label in labels]
+        else:
+            names = [self.error_type] * len(labels)
+        return np.asarray([ops.POSE_ERR_MODES[m] for m in names], dtype=np.int32)
+
+    def _device_errors(self, modes, TXO_pred, TXO_gt, labels, K) -> Dict[str, torch.Tensor]:
+        """The one device call of the meter: rows (pred n, gt n, object of label n)."""
+        ids = torch.arange(len(labels), dtype=torch.int32)
+        obj_ids = self.mesh_db.ids_of(labels)
+        if self.sample_n_points is not None:  # non-exact only: the reference's deterministic subset of the padded table
+            t = self.mesh_db.device_tables
+            pick = torch.as_tensor(ops.sample_point_ids(t["points"].shape[1], self.sample_n_points)).to(t["points"].device)
+            points = t["points"][:, pick].contiguous()
+            n_pts = torch.full((points.shape[0],), points.shape[1], dtype=torch.int32, device=points.device)
+            return ops.pose_errors_tables(ids, ids, obj_ids, modes, TXO_pred, TXO_gt, points, t["symmetries"], t["n_sym"], n_pts, K=K)
+        return ops.pose_errors(ids, ids, obj_ids, modes, TXO_pred, TXO_gt, self.mesh_db, K=K, exact_meshes=self.exact_meshes)
+
+    def compute_errors(self, TXO_pred, TXO_gt, labels, K=None):
+        """``norm_avg [b]``, ``xyz_avg [b, 3]``, ``TCO_xyz [b, 3]``, ``TCO_norm [b]`` as in the reference, plus ``norm_max [b]`` and
+        ``sym_id [b]``; any batch size, exact meshes included."""
+        if len(labels) == 0:
+            return {"norm_avg": torch.empty(0, dtype=torch.float), "xyz_avg": torch.empty(0, 3, dtype=torch.float),
+                    "norm_max": torch.empty(0, dtype=torch.float), "sym_id": torch.empty(0, dtype=torch.int32),
+                    "TCO_xyz": torch.empty((0, 3), dtype=torch.float), "TCO_norm": torch.empty(0, dtype=torch.float)}
+        if self.error_type == "MSPD" and K is None:
+            raise ValueError("MSPD needs the camera intrinsics K [b, 3, 3]")
+        return self._device_errors(self._row_modes(labels), TXO_pred, TXO_gt, np.asarray(labels), K if self.error_type == "MSPD" else None)
+
+    def compute_errors_batch(self, TXO_pred, TXO_gt, labels, K=None):
+        """The reference cut the candidates into batches of ``errors_bsz``; one launch scores them all."""
+        return self.compute_errors(TXO_pred, TXO_gt, labels, K=K)
+
+    # -- accumulation --------------------------------------------------------------------------------------------------------------
+    def add(self, pred_data, gt_data):
+        keys = list(GROUP_KEYS)
+        pred_data, gt_data = pred_data.float(), gt_data.float()
+        diameter = lambda labels: np.asarray([self.mesh_db.infos[k]["diameter_m"] for k in labels], dtype=float)  # noqa: E731
+
+        # predictions of the scenes and views the ground truth covers
+        gt_views = gt_data.infos.loc[:, ["scene_id", "view_id"]].drop_duplicates().reset_index(drop=True)
+        targets = self.targets
+        if targets is not None:
+            targets = gt_views.merge(targets)
+        pred_data.infos["batch_pred_id"] = np.arange(len(pred_data))
+        pred_data = pred_data[gt_views.merge(pred_data.infos)["batch_pred_id"].to_numpy()]
+
+        pred_data.infos = add_inst_num(pred_data.infos, key="pred_inst_id", group_keys=keys)
+        gt_data.infos = add_inst_num(gt_data.infos, key="gt_inst_id", group_keys=keys)
+
+        # BOP: the best n predictions of a group
+        if not self.consider_all_predictions:
+            top = get_top_n_ids(pred_data.infos, group_keys=keys, top_key="score", targets=targets, n_top=self.n_top)
+            kept = pred_data.clone()[np.asarray(top, dtype=int)]
+        else:
+            kept = pred_data.clone()
+
+        gt_data.infos = add_valid_gt(gt_data.infos, group_keys=keys, targets=targets, visib_gt_min=self.visib_gt_min)
+        cands = get_candidate_matches(kept.infos, gt_data.infos, group_keys=keys, only_valids=True)
+
+        # candidates whose bounding spheres do not even overlap are dropped before any error is computed
+        if self.spheres_overlap_check:
+            dt = kept.poses[cands["pred_id"].to_numpy(), :3, -1] - gt_data.poses[cands["gt_id"].to_numpy(), :3, -1]
+            overlap = torch.norm(dt, dim=-1) < torch.as_tensor(diameter(cands["label"])).to(dt.dtype).to(dt.device)
+            cands = cands.iloc[np.where(overlap.cpu().numpy())[0]].reset_index(drop=True)
+            cands["cand_id"] = np.arange(len(cands))
+
+        pred_ids, gt_ids = cands["pred_id"].to_numpy(), cands["gt_id"].to_numpy()
+        K = gt_data.K[gt_ids] if self.error_type == "MSPD" else None
+        errors = self.compute_errors_batch(kept.poses[pred_ids], gt_data.poses[gt_ids], cands["label"].to_numpy(), K=K)
+        errors = {k: v.cpu().numpy() for k, v in errors.items()}
+        metric = errors["norm_max" if self.error_type in _MAX_ERRORS else "norm_avg"]
+
+        # BOP: only errors within the threshold can be matches
+        cands["error"] = metric
+        cands["obj_diameter"] = diameter(cands["label"])
+        in_pixels = self.error_type == "MSPD"
+        limit = self.match_threshold if in_pixels else self.match_threshold * cands["obj_diameter"]
+        cands = cands[cands["error"] <= limit].reset_index(drop=True)
+        matches = match_poses(cands, group_keys=keys)
+
+        gt_keys = [*keys, "gt_inst_id", "valid"] + (["visib_fract"] if "visib_fract" in gt_views else [])
+        gt = gt_data.infos.loc[:, gt_keys].reset_index(drop=True)
+        preds = pred_data.infos.loc[:, [*keys, "pred_inst_id", "score"]].reset_index(drop=True)
+        matches = matches.loc[:, [*keys, "pred_inst_id", "gt_inst_id", "cand_id"]].reset_index(drop=True)
+
+        cand_id = matches["cand_id"].to_numpy(dtype=int)
+        matches["obj_diameter"] = diameter(matches["label"])
+        matches["norm"] = metric[cand_id]
+        matches["0.1d"] = metric[cand_id] < (self.match_threshold if in_pixels else 0.1 * matches["obj_diameter"].to_numpy())
+        matches["xyz"] = _array_column(errors["xyz_avg"][cand_id])
+        matches["TCO_xyz"] = _array_column(errors["TCO_xyz"][cand_id])
+        matches["TCO_norm"] = errors["TCO_norm"][cand_id]
+        preds["TXO_pred"] = _array_column(pred_data.poses.cpu().numpy())
+
+        matches = _left_join(matches, preds, [*keys, "pred_inst_id"])
+        gt = _left_join(gt, matches, [*keys, "gt_inst_id"])
+        preds["0.1d"] = _left_join(preds, matches, [*keys, "pred_inst_id"])["0.1d"].to_numpy()
+
+        self.datas["gt_df"].append(gt)
+        self.datas["pred_df"].append(preds)
+        self.datas["matches_df"].append(matches)
+
+    def summary(self):
+        gt_df = pd.concat(self.datas["gt_df"], ignore_index=True)
+        matches_df = pd.concat(self.datas["matches_df"], ignore_index=True)
+        pred_df = pd.concat(self.datas["pred_df"], ignore_index=True)
+
+        valid_df = gt_df[gt_df["valid"].to_numpy(dtype=bool)]
+        AUC = OrderedDict()
+        for label, group in valid_df.groupby("label"):
+            errors = group["norm"].to_numpy()
+            assert np.all(~np.isnan(errors))
+            AUC[label] = compute_auc_posecnn(errors)
+        gt_df.attrs["AUC/objects"] = pd.Series(AUC, dtype=float)
+        gt_df.attrs["AUC/objects/mean"] = float(np.nanmean(list(AUC.values()))) if np.isfinite(list(AUC.values())).any() else np.nan
+        gt_df.attrs["AUC"] = compute_auc_posecnn(valid_df["norm"].to_numpy())
+
+        # ground truths per label that count for AP / mAP at 0.1 d
+        valid_k = "0.1d"
+        keys = list(GROUP_KEYS)
+        if self.n_top > 0:
+            per_group = gt_df[[*keys, "valid"]].groupby(keys).sum().reset_index()
+            per_group["gt_count"] = np.minimum(self.n_top, per_group["valid"])
+            n_gts = {label: group["gt_count"].sum() for label, group in per_group.groupby("label")}
+        else:
+            n_gts = gt_df[["label", "valid"]].groupby("label")["valid"].sum().to_dict()
+
+        def compute_ap(label_df, label_n_gt):
+            label_df = label_df.sort_values("score", ascending=False).reset_index(drop=True)
+            label_df["n_tp"] = np.cumsum(label_df[valid_k].to_numpy().astype(float))
+            label_df["prec"] = label_df["n_tp"] / (np.arange(len(label_df)) + 1)
+            label_df["recall"] = label_df["n_tp"] / label_n_gt
+            y_true = label_df[valid_k].to_numpy(dtype=bool)
+            ap = average_precision(y_true, label_df["score"]) * y_true.sum() / label_n_gt
+            label_df["AP"] = ap
+            label_df["n_gt"] = label_n_gt
+            return ap, label_df
+
+        ap_dfs = {}
+        df = pred_df[["label", valid_k, "score"]].set_index("label")
+        for label, label_n_gt in n_gts.items():
+            if label in df.index:  # the reference's `df.index.contains(label)`, which pandas removed in 1.0
+                label_df = df.loc[[label]]
+                if label_df[valid_k].sum() > 0:
+                    _, ap_dfs[label] = compute_ap(label_df, label_n_gt)
+        if ap_dfs:
+            mAP = np.mean([np.unique(ap_df["AP"]).item() for ap_df in ap_dfs.values()])
+            AP, ap_dfs["all"] = compute_ap(df.reset_index(), sum(n_gts.values()))
+        else:
+            AP, mAP = 0.0, 0.0
+        n_gt_valid = int(sum(n_gts.values()))
+
+        summary = {
+            "n_gt": len(gt_df),
+            "n_gt_valid": n_gt_valid,
+            "n_pred": len(pred_df),
+            "n_matched": len(matches_df),
+            "matched_gt_ratio": len(matches_df) / n_gt_valid,
+            "pred_matched_ratio": len(pred_df) / max(len(matches_df), 1),
+            "0.1d": float(valid_df[valid_k].sum()) / n_gt_valid,
+        }
+        if self.report_error_stats:
+            mean_of = lambda col: np.mean(np.stack(list(matches_df[col])), axis=0).tolist() if len(matches_df) else [np.nan] * 3  # noqa: E731
+            summary.update({"norm": float(matches_df["norm"].mean()), "xyz": mean_of("xyz"), "TCO_xyz": mean_of("TCO_xyz"),
+                            "TCO_norm": float(matches_df["TCO_norm"].mean())})
+        if self.report_AP:
+            summary.update({"AP": AP, "mAP": mAP})
+        if self.report_error_AUC:
+            summary.update({"AUC/objects/mean": gt_df.attrs["AUC/objects/mean"], "AUC": gt_df.attrs["AUC"]})
+        return summary, {"gt": gt_df, "matches": matches_df, "preds": pred_df, "ap": ap_dfs}

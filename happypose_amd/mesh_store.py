@@ -209,6 +209,8 @@ class MeshDataBase:
                 points = np.asarray(self.meshes[label].vertices) * obj.scale
                 extent = points.max(0) - points.min(0)
                 obj.diameter_meters = float(np.linalg.norm(extent))
+            # what the evaluation reads per label (CP/lib3d/rigid_mesh_database.py keeps the object's dict as its infos)
+            self.infos[label].update(diameter_m=obj.diameter_meters, is_symmetric=obj.is_symmetric)
 
     @staticmethod
     def from_object_ds(object_ds: RigidObjectDataset) -> "MeshDataBase":

@@ -923,9 +923,11 @@ def ransac_find_inliers(seeds_view1, seeds_view2, hypothesis_id, cand1, cand2, d
             "best_hypotheses": best[:nb.value].copy()}
 
 
-def _mv_tables(mesh_db):
-    """Device tables of a ``BatchedMeshes`` that went through ``.to(device)``: (points, symmetries, n_sym, n_obj, n_pts, s_max)."""
-    if getattr(mesh_db, "unsupported_symmetries", None):
+def _mv_tables(mesh_db, reads_symmetries: bool = True):
+    """Device tables of a ``BatchedMeshes`` that went through ``.to(device)``: (points, symmetries, n_sym, n_obj, n_pts, s_max).
+    ``reads_symmetries=False``: the caller's kernel modes never open the symmetry table (ADD, ADD-S), so labels whose
+    symmetries could not be tabulated are no obstacle."""
+    if reads_symmetries and getattr(mesh_db, "unsupported_symmetries", None):
         raise ValueError("continuous symmetries with an offset or an axis other than +x / +y / +z are not supported "
                          f"(make_bop_symmetries): {mesh_db.unsupported_symmetries}")
     t = getattr(mesh_db, "device_tables", None)
@@ -1052,3 +1054,87 @@ def mv_score_seed_matches(seeds, tmatches, TC1C2: torch.Tensor, poses: torch.Ten
                                              ptr(poses), ptr(cand_obj), n_cand, ptr(pts), ptr(sym), ptr(n_sym), n_obj, n_pts, s_max,
                                              ptr(dists), stream_ptr(dev)), "hp_mv_score_seed_matches")
     return dists
+
+
+# ---- pose-error metrics (csrc/pose_errors.hip) ---------------------------------------------------------------------------------
+POSE_ERR_MODES = {"ADD": 0, "ADD-S": 1, "ADD-SYM": 2, "MSSD": 3, "MSPD": 4}  # HP_POSE_ERR_*
+POSE_ERR_PRED_TILE, POSE_ERR_GT_BLOCK = 512, 1024  # HP_POSE_ERR_PRED_TILE / HP_POSE_ERR_GT_BLOCK (tests/test_pose_errors_host.py)
+_POSE_ERR_MAX_ROWS = 65535  # rows of one hp_pose_errors call
+_POSE_ERR_READS_SYM = (2, 3, 4)
+
+
+def pose_errors_workspace_bytes(n_rows: int, max_pts: int) -> int:
+    """``hp_pose_errors_workspace_bytes``: rows x blocks of ground-truth points x 32 bytes."""
+    n = int(lib().hp_pose_errors_workspace_bytes(int(n_rows), int(max_pts)))
+    assert n >= 0, "pose_errors_workspace_bytes: n_rows >= 0 and max_pts >= 1"
+    return n
+
+
+def pose_errors_tables(pred_id, gt_id, obj_id, mode, poses_pred: torch.Tensor, poses_gt: torch.Tensor, points: torch.Tensor,
+                       symmetries: torch.Tensor, n_sym: torch.Tensor, n_pts: torch.Tensor, K: Optional[torch.Tensor] = None,
+                       return_assign: bool = False) -> Dict[str, torch.Tensor]:
+    """``hp_pose_errors`` on explicit device tables (``points [n_obj, max_pts, 3]``, ``symmetries [n_obj, s_max, 4, 4]``,
+    ``n_sym`` / ``n_pts [n_obj]`` int32).  Row ``r`` scores ``poses_pred[pred_id[r]]`` against ``poses_gt[gt_id[r]]`` on object
+    ``obj_id[r]`` in mode ``mode[r]`` (``POSE_ERR_MODES`` values); ``K [n_rows, 3, 3]`` for MSPD rows.  Returns ``norm_avg``,
+    ``xyz_avg [n, 3]``, ``norm_max``, ``sym_id``, ``TCO_xyz [n, 3]``, ``TCO_norm`` and, on request, ``assign [n, max_pts]``."""
+    dev = points.device
+    n_obj, max_pts, s_max = points.shape[0], points.shape[1], symmetries.shape[1]
+    assert points.shape == (n_obj, max_pts, 3) and symmetries.shape == (n_obj, s_max, 4, 4)
+    assert n_sym.shape == (n_obj,) and n_sym.dtype == torch.int32 and n_pts.shape == (n_obj,) and n_pts.dtype == torch.int32
+    n_pred, n_gt = poses_pred.shape[0], poses_gt.shape[0]
+    assert poses_pred.shape == (n_pred, 4, 4) and poses_gt.shape == (n_gt, 4, 4)
+    n = len(pred_id)
+    assert len(gt_id) == len(obj_id) == len(mode) == n
+    _check_ids(pred_id, n_pred, "pose_errors: pred_id")
+    _check_ids(gt_id, n_gt, "pose_errors: gt_id")
+    _check_ids(obj_id, n_obj, "pose_errors: obj_id")
+    _check_ids(mode, len(POSE_ERR_MODES), "pose_errors: mode")
+    # a mode column still on the host says whether any row is ADD-S: without one the ADD-S launches and their workspace are skipped
+    host_mode = torch.as_tensor(mode)
+    host_mode = host_mode.numpy() if host_mode.device.type == "cpu" else None
+    pred_id, gt_id, obj_id, mode = (_i32(a, dev) for a in (pred_id, gt_id, obj_id, mode))
+    poses_pred, poses_gt, points, symmetries = (_f32(t, dev) for t in (poses_pred, poses_gt, points, symmetries))
+    n_sym, n_pts = n_sym.to(dev).contiguous(), n_pts.to(dev).contiguous()
+    if K is not None:
+        assert K.shape == (n, 3, 3), "pose_errors: one K per row"
+        K = _f32(K, dev)
+    out = {"norm_avg": torch.empty(n, dtype=torch.float32, device=dev), "xyz_avg": torch.empty(n, 3, dtype=torch.float32, device=dev),
+           "norm_max": torch.empty(n, dtype=torch.float32, device=dev), "sym_id": torch.empty(n, dtype=torch.int32, device=dev),
+           "TCO_xyz": torch.empty(n, 3, dtype=torch.float32, device=dev), "TCO_norm": torch.empty(n, dtype=torch.float32, device=dev)}
+    if return_assign:
+        out["assign"] = torch.empty(n, max_pts, dtype=torch.int32, device=dev)
+    step = _POSE_ERR_MAX_ROWS
+    if return_assign:
+        step = max(1, min(step, ((1 << 31) - 1) // max_pts))
+    with torch.cuda.device(dev):
+        for r0 in range(0, max(n, 1), step):  # one launch for anything an evaluation batch holds; chunks only past the grid limit
+            m = min(step, n - r0)
+            sl = slice(r0, r0 + m)
+            n_add_s = -1 if host_mode is None else int((host_mode[sl] == POSE_ERR_MODES["ADD-S"]).sum())
+            nbytes = pose_errors_workspace_bytes(m, max_pts) if n_add_s else 0
+            ws = torch.empty(nbytes // 4, dtype=torch.float32, device=dev) if nbytes else None
+            check(lib().hp_pose_errors(m, ptr(pred_id[sl]), ptr(gt_id[sl]), ptr(obj_id[sl]), ptr(mode[sl]), n_add_s, ptr(poses_pred), n_pred,
+                                       ptr(poses_gt), n_gt, ptr(K[sl]) if K is not None else None, ptr(points), ptr(symmetries),
+                                       ptr(n_sym), ptr(n_pts), n_obj, max_pts, s_max, ptr(out["norm_avg"][sl]), ptr(out["xyz_avg"][sl]),
+                                       ptr(out["norm_max"][sl]), ptr(out["sym_id"][sl]), ptr(out["TCO_xyz"][sl]),
+                                       ptr(out["TCO_norm"][sl]), ptr(out["assign"][sl]) if return_assign else None, ptr(ws),
+                                       nbytes, stream_ptr(dev)), "hp_pose_errors")
+    return out
+
+
+def pose_errors(pred_id, gt_id, obj_id, mode, poses_pred: torch.Tensor, poses_gt: torch.Tensor, mesh_db,
+                K: Optional[torch.Tensor] = None, exact_meshes: bool = True, return_assign: bool = False):
+    """``hp_pose_errors`` on the device tables of ``mesh_db`` (``MeshDataBase.batched().to(device)``).  ``exact_meshes=True``
+    counts each object's own ``n_points`` (the reference's exact mode), ``False`` the whole padded table.  ``mode``: one
+    ``POSE_ERR_MODES`` value per row, on the host -- the symmetry-reading modes refuse a ``mesh_db`` with
+    ``unsupported_symmetries`` like the multi-view wrappers; a ``mode`` column that already lives on the device cannot be
+    inspected and is treated as reading symmetries."""
+    m = torch.as_tensor(mode)
+    reads_sym = m.device.type != "cpu" or bool(np.isin(m.numpy(), _POSE_ERR_READS_SYM).any())
+    pts, sym, n_sym, n_obj, n_pad, s_max = _mv_tables(mesh_db, reads_symmetries=reads_sym)
+    if exact_meshes:
+        n_pts = torch.as_tensor(np.asarray([mesh_db.infos[label]["n_points"] for label in mesh_db.labels], dtype=np.int32)).to(pts.device)
+    else:
+        n_pts = torch.full((n_obj,), n_pad, dtype=torch.int32, device=pts.device)
+    return pose_errors_tables(pred_id, gt_id, obj_id, mode, poses_pred, poses_gt, pts, sym, n_sym, n_pts, K=K,
+                              return_assign=return_assign)

@@ -700,6 +700,56 @@ int hp_ransac_find_inliers(int64_t n_hyp, const int32_t* h_view1, const int32_t*
                            float dist_threshold, int n_min_inliers, int32_t* h_inlier_cand1, int32_t* h_inlier_cand2,
                            int64_t* n_inliers, int32_t* h_best_hypotheses, int64_t* n_best);
 
+/* ------------------------------------------------------------------------------------
+ * Pose-error metrics of the evaluation: dists_add / dists_add_symmetric / dists_add_symmetries (TB/lib3d/distances.py),
+ * chamfer_dist (CP/lib3d/symmetric_distances.py:58-78), the errors of PoseErrorMeter.compute_errors
+ * (CP/evaluation/meters/pose_meters.py:60-116) and BOP's MSSD / MSPD.  csrc/pose_errors.hip.
+ *
+ * Row r is the triple (d_poses_pred[d_pred_id[r]], d_poses_gt[d_gt_id[r]], object d_obj_id[r]) with the mode d_mode[r]; the
+ * four index columns are int32 [n_rows] on the device.  Mesh tables as in the multi-view section (d_points
+ * [n_obj][max_pts][3], d_symmetries [n_obj][s_max][16], d_n_sym [n_obj]) plus d_n_pts [n_obj]: how many of the max_pts points of
+ * an object count -- its own n_points for the reference's exact_meshes=True, max_pts for the padded table (padding repeats
+ * vertices and the reference's non-exact mode counts them).  With p_j the object's points and d_j a per-point difference:
+ *  HP_POSE_ERR_ADD      d_j = T_gt p_j - T_pred p_j
+ *  HP_POSE_ERR_ADD_S    for every ground-truth point j the predicted point i with the smallest squared distance
+ *                       dx^2 + dy^2 + dz^2 (computed from the differences, never from expanded norms), the lowest i on an exact
+ *                       tie; d_j = T_gt p_j - T_pred p_i
+ *  HP_POSE_ERR_ADD_SYM  over the object's n_sym symmetries S, T_gt S with the smallest mean |d_j| against T_pred (first strict
+ *                       minimum); d_j for that S
+ *  HP_POSE_ERR_MSSD     the S with the smallest max_j |T_pred p_j - T_gt S p_j| (first strict minimum); d_j for that S
+ *  HP_POSE_ERR_MSPD     the same with both sides projected by d_K [n_rows][9] (project_points: K T p, divided by its third
+ *                       component), d_j = (du, dv, 0) in pixels.  d_K may be NULL when no row asks for it.
+ * ADD(-S) is not a mode: the caller sets ADD or ADD-S per row from the object's is_symmetric.
+ * n_add_s: how many rows are ADD-S if the caller knows it, negative if it does not.  0 skips the ADD-S launches (blocks x n_rows
+ * workgroups that would only read the index columns) and needs no workspace; an ADD-S row in such a call is answered like a
+ * guarded row.
+ * Outputs per row: d_norm_avg = mean |d_j|, d_xyz_avg [.][3] = mean of the absolute components, d_norm_max = max |d_j| (for MSSD
+ * and MSPD this IS the metric), d_sym_id = the chosen symmetry (-1 in ADD and ADD-S), d_TCO_xyz [.][3] = |t_pred - t_gt| and
+ * d_TCO_norm its length.  d_assign [n_rows][max_pts] (may be NULL): in ADD-S the chosen i of every j, in every other mode j; -1
+ * past the object's n_pts.
+ * An index outside its table, an n_sym outside 1..s_max, an n_pts outside 1..max_pts, an unknown mode or MSPD without d_K
+ * give NaN in every float output of that row (sym_id and assign -1); such a row reads nothing outside the tables.
+ * n_rows == 0 returns HP_OK before anything else is looked at and launches nothing; at most 65535 rows per call.
+ * ADD-S: a workgroup is one (row, block of HP_POSE_ERR_GT_BLOCK ground-truth points), the predicted points pass through LDS in
+ * tiles of HP_POSE_ERR_PRED_TILE; per-block partial sums go to d_workspace (hp_pose_errors_workspace_bytes(n_rows, max_pts)
+ * bytes: n_rows x blocks x 32, nothing of size max_pts^2) and are added in block order.  No atomics: a row's outputs do not depend
+ * on the other rows of the call and are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------- */
+#define HP_POSE_ERR_ADD 0
+#define HP_POSE_ERR_ADD_S 1
+#define HP_POSE_ERR_ADD_SYM 2
+#define HP_POSE_ERR_MSSD 3
+#define HP_POSE_ERR_MSPD 4
+#define HP_POSE_ERR_PRED_TILE 512
+#define HP_POSE_ERR_GT_BLOCK 1024
+int64_t hp_pose_errors_workspace_bytes(int n_rows, int max_pts);
+int hp_pose_errors(int n_rows, const int32_t* d_pred_id, const int32_t* d_gt_id, const int32_t* d_obj_id, const int32_t* d_mode,
+                   int n_add_s, const float* d_poses_pred, int n_pred, const float* d_poses_gt, int n_gt, const float* d_K,
+                   const float* d_points, const float* d_symmetries, const int32_t* d_n_sym, const int32_t* d_n_pts, int n_obj,
+                   int max_pts, int s_max, float* d_norm_avg, float* d_xyz_avg, float* d_norm_max, int32_t* d_sym_id,
+                   float* d_TCO_xyz, float* d_TCO_norm, int32_t* d_assign, void* d_workspace, int64_t workspace_bytes,
+                   void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -159,6 +159,12 @@ _PROTOS = {
     "hp_pose_errors": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p,
                                  c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_i32p,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_scene_compose": (C.c_int, [C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p,
+                                   c_u8p, C.c_void_p]),
+    "hp_scene_visibility": (C.c_int, [C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, c_i32p, C.c_void_p]),
+    "hp_scene_contour": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_u8p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_u8p,
+                                   c_u8p, C.c_void_p]),
+    "hp_scene_overlay": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

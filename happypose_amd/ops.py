@@ -1138,3 +1138,109 @@ def pose_errors(pred_id, gt_id, obj_id, mode, poses_pred: torch.Tensor, poses_gt
         n_pts = torch.full((n_obj,), n_pad, dtype=torch.int32, device=pts.device)
     return pose_errors_tables(pred_id, gt_id, obj_id, mode, poses_pred, poses_gt, pts, sym, n_sym, n_pts, K=K,
                               return_assign=return_assign)
+
+
+# --------------------------------------------------------------------------------------------------------------- scenes (scene.hip)
+SCENE_VIS_FIELDS = 10  # HP_SCENE_VIS_FIELDS
+SCENE_MAX_DILATE = 3   # HP_SCENE_MAX_DILATE
+SCENE_VIS_COLUMNS = ("px_count_all", "px_count_visib", "all_x_min", "all_y_min", "all_x_max", "all_y_max",
+                     "visib_x_min", "visib_y_min", "visib_x_max", "visib_y_max")
+
+
+def _scene_layers(layer_off, depth: torch.Tensor):
+    """Checks shared by the layer-reading wrappers: ``layer_off`` [n_cam + 1] (checked where it still lives on the host: starts
+    at 0, ascends, ends at the layer count) and ``depth`` [L, 1, H, W] float32 on the device."""
+    assert depth.dim() == 4 and depth.shape[1] == 1 and depth.dtype == torch.float32 and depth.is_cuda, "layer depth: [L, 1, H, W] float32 on the device"
+    n_layers, _, h, w = depth.shape
+    off = torch.as_tensor(layer_off)
+    assert off.dim() == 1 and off.numel() >= 1, "layer_off: [n_cam + 1]"
+    if off.device.type == "cpu":
+        o = off.numpy().astype(np.int64)
+        assert o[0] == 0 and o[-1] == n_layers and (np.diff(o) >= 0).all(), f"layer_off {o.tolist()} does not partition {n_layers} layers"
+    return _i32(off, depth.device), off.numel() - 1, n_layers, h, w
+
+
+def scene_compose(layer_off, rgb: torch.Tensor, nrm: Optional[torch.Tensor], depth: torch.Tensor) -> Dict[str, Optional[torch.Tensor]]:
+    """``hp_scene_compose``: per-pixel z-merge of rasterised layers (``rasterize(..., render_depth=True)`` outputs: ``rgb`` /
+    ``nrm`` [L, 3, H, W], ``depth`` [L, 1, H, W], 0 = background), sorted by camera with ``layer_off`` [n_cam + 1] giving each
+    camera's range.  The winner of a pixel is the camera's layer with the smallest depth > 0, the lowest layer on a tie.  Returns
+    ``rgb`` [n_cam, 3, H, W], ``normals`` (or None), ``depth`` [n_cam, 1, H, W], ``ids`` [n_cam, H, W] int32 (index within the
+    camera, -1 = nothing) and ``mask`` [n_cam, 1, H, W] uint8 -- copies of the winner's values, bit for bit."""
+    dev = depth.device
+    off, n_cam, n_layers, h, w = _scene_layers(layer_off, depth)
+    assert rgb.shape == (n_layers, 3, h, w) and rgb.dtype == torch.float32 and rgb.device == dev, "layer rgb: [L, 3, H, W] float32"
+    assert nrm is None or (nrm.shape == (n_layers, 3, h, w) and nrm.dtype == torch.float32 and nrm.device == dev), "layer normals: [L, 3, H, W] float32"
+    rgb, depth = rgb.contiguous(), depth.contiguous()
+    nrm = None if nrm is None else nrm.contiguous()
+    out = {"rgb": torch.empty((n_cam, 3, h, w), dtype=torch.float32, device=dev),
+           "normals": torch.empty((n_cam, 3, h, w), dtype=torch.float32, device=dev) if nrm is not None else None,
+           "depth": torch.empty((n_cam, 1, h, w), dtype=torch.float32, device=dev),
+           "ids": torch.empty((n_cam, h, w), dtype=torch.int32, device=dev),
+           "mask": torch.empty((n_cam, 1, h, w), dtype=torch.uint8, device=dev)}
+    with torch.cuda.device(dev):
+        check(lib().hp_scene_compose(n_cam, ptr(off), n_layers, h, w, ptr(rgb), ptr(nrm), ptr(depth), ptr(out["rgb"]), ptr(out["normals"]),
+                                     ptr(out["depth"]), ptr(out["ids"]), ptr(out["mask"]), stream_ptr(dev)), "hp_scene_compose")
+    return out
+
+
+def scene_visibility(layer_off, depth: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """``hp_scene_visibility``: int32 [L, 10] (``SCENE_VIS_COLUMNS``) -- pixel counts of every layer alone and as visible in the
+    composed ``ids`` [n_cam, H, W], with the two inclusive bounding boxes (-1 where the count is 0)."""
+    dev = depth.device
+    off, n_cam, n_layers, h, w = _scene_layers(layer_off, depth)
+    assert ids.shape == (n_cam, h, w) and ids.dtype == torch.int32 and ids.device == dev, "ids: [n_cam, H, W] int32"
+    table = torch.empty((n_layers, SCENE_VIS_FIELDS), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_scene_visibility(n_cam, ptr(off), n_layers, h, w, ptr(depth.contiguous()), ptr(ids.contiguous()), ptr(table),
+                                        stream_ptr(dev)), "hp_scene_visibility")
+    return table
+
+
+def _u8_frames(t: torch.Tensor, what: str) -> torch.Tensor:
+    assert t.dim() == 4 and t.shape[-1] == 3 and t.dtype == torch.uint8 and t.is_cuda, f"{what}: [n, H, W, 3] uint8 on the device"
+    return t.contiguous()
+
+
+def scene_contour(frame: torch.Tensor, mask: Optional[torch.Tensor] = None, ids: Optional[torch.Tensor] = None, per_object: bool = False,
+                  color: Tuple[int, int, int] = (0, 255, 0), dilate_iterations: int = 1, return_edge: bool = True):
+    """``hp_scene_contour``: a copy of ``frame`` [n, H, W, 3] uint8 with the outline of ``mask`` ([n, H, W] or [n, 1, H, W]
+    uint8 / bool) or of ``ids`` [n, H, W] int32 (``per_object``: between objects too) painted in ``color``, and the edge map
+    [n, H, W] uint8 (0 / 255).  The outline's definition is in the header."""
+    frame = _u8_frames(frame, "frame")
+    n, h, w, _ = frame.shape
+    dev = frame.device
+    assert (mask is None) != (ids is None), "scene_contour: exactly one of mask and ids"
+    if mask is not None:
+        assert mask.numel() == n * h * w and mask.dtype in (torch.uint8, torch.bool) and mask.device == dev, "mask: [n, H, W] uint8 / bool"
+        mask = mask.contiguous().view(torch.uint8)
+    else:
+        assert ids.shape == (n, h, w) and ids.dtype == torch.int32 and ids.device == dev, "ids: [n, H, W] int32"
+        ids = ids.contiguous()
+    out = torch.empty_like(frame)
+    edge = torch.empty((n, h, w), dtype=torch.uint8, device=dev) if return_edge else None
+    r, g, b = (int(c) for c in color)
+    with torch.cuda.device(dev):
+        check(lib().hp_scene_contour(n, h, w, ptr(frame), ptr(mask), ptr(ids), 1 if per_object else 0, r, g, b, int(dilate_iterations),
+                                     ptr(out), ptr(edge), stream_ptr(dev)), "hp_scene_contour")
+    return out, edge
+
+
+def scene_overlay(rgb_input: torch.Tensor, rgb_rendered: torch.Tensor, lut_render: torch.Tensor, lut_input: torch.Tensor,
+                  mask: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_scene_overlay`` on [n, H, W, 3] uint8 frames with the two 256-entry uint8 tables of
+    ``happypose_amd.scene.overlay_tables``; ``mask`` ([n, H, W] / [n, 1, H, W] uint8 / bool) replaces "any render channel > 0"."""
+    rgb_input, rgb_rendered = _u8_frames(rgb_input, "rgb_input"), _u8_frames(rgb_rendered, "rgb_rendered")
+    assert rgb_input.shape == rgb_rendered.shape and rgb_input.device == rgb_rendered.device
+    n, h, w, _ = rgb_input.shape
+    dev = rgb_input.device
+    for t in (lut_render, lut_input):
+        assert t.shape == (256,) and t.dtype == torch.uint8, "overlay tables: 256 uint8 entries"
+    lut_render, lut_input = lut_render.to(dev).contiguous(), lut_input.to(dev).contiguous()
+    if mask is not None:
+        assert mask.numel() == n * h * w and mask.dtype in (torch.uint8, torch.bool) and mask.device == dev, "mask: [n, H, W] uint8 / bool"
+        mask = mask.contiguous().view(torch.uint8)
+    out = torch.empty_like(rgb_input)
+    with torch.cuda.device(dev):
+        check(lib().hp_scene_overlay(n, h, w, ptr(rgb_input), ptr(rgb_rendered), ptr(mask), ptr(lut_render), ptr(lut_input), ptr(out),
+                                     stream_ptr(dev)), "hp_scene_overlay")
+    return out

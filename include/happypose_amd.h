@@ -750,6 +750,60 @@ int hp_pose_errors(int n_rows, const int32_t* d_pred_id, const int32_t* d_gt_id,
                    float* d_TCO_xyz, float* d_TCO_norm, int32_t* d_assign, void* d_workspace, int64_t workspace_bytes,
                    void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Multi-object scenes: Panda3dSceneRenderer.render_scene(object_datas, camera_datas, light_datas, ...)
+ * (TB/renderer/panda3d_scene_renderer.py:320-390), the gt-info quantities of MP/scripts/bop_calc_gt_info.py (px_count_all,
+ * px_count_visib, bbox_obj, bbox_visib), make_contour_overlay (TB/visualization/utils.py:54-82) and BokehPlotter.plot_overlay
+ * (TB/visualization/bokeh_plotter.py:116-141).  csrc/scene.hip.
+ *
+ * hp_rasterize draws one object per view, so a scene is rendered as LAYERS: one view per (camera, object) pair, sorted by
+ * camera.  d_layer_off [n_cam + 1] (device, int32) holds every camera's range into the layer buffers; all cameras of a call share
+ * h x w.  The layer buffers are NCHW as hp_rasterize writes them: d_layer_rgb [n_layers][3][h][w], d_layer_nrm the same or NULL,
+ * d_layer_depth [n_layers][1][h][w] in metres with 0 = background.  A camera may own no layer.  Offsets are clamped into
+ * [0, n_layers] on the device: a corrupt table reads nothing outside the buffers.
+ *
+ * hp_scene_compose: at every pixel the winner is the layer of that camera with the smallest depth > 0, the LOWEST layer on a tie
+ * (NaN and +inf never win).  d_rgb [n_cam][3][h][w], d_nrm the same (NULL: not wanted; needs d_layer_nrm), d_depth
+ * [n_cam][1][h][w], d_ids [n_cam][h][w] int32 = the winner's index WITHIN its camera, d_mask [n_cam][1][h][w] u8.  Without a
+ * winner: colour, normals and depth 0, id -1, mask 0.  Values are copies of the winner's -- no arithmetic -- so the outputs are a
+ * bit-exact function of the layers.
+ * LIMITATION: every layer was resolved on its own, 4x multisampled against black (HP_RASTER_MSAA4): where the silhouette of a
+ * nearer object crosses a farther one, the nearer layer's edge pixels blend with black instead of with the object behind, in a
+ * band at most one pixel wide.  Depth, ids, mask and visibility are exact; single-sampled layers compose to exactly the colours
+ * of one shared z-buffer.
+ *
+ * hp_scene_visibility: d_table [n_layers][HP_SCENE_VIS_FIELDS] int32 = px_count_all (layer depth > 0), px_count_visib (d_ids of
+ * the layer's camera equals the layer's index within it), bbox_all (x_min, y_min, x_max, y_max inclusive), bbox_visib (the same of
+ * the visible pixels); every field of a box whose count is 0 is -1.  The call initialises the table, then counts with integer
+ * atomics: the result does not depend on the launch order.  visib_fract = px_count_visib / px_count_all is the host's division.
+ *
+ * hp_scene_contour: d_out [n_cam][h][w][3] u8 = d_frame with the outline painted in (color_r, color_g, color_b), d_edge
+ * [n_cam][h][w] u8 (may be NULL) = 255 on the outline, else 0.  The region is given by exactly one of d_mask [n_cam][h][w] u8
+ * (non-zero = inside) and d_ids [n_cam][h][w] int32 (>= 0 = inside).  Definition (this library's own: the reference runs
+ * cv2.Canny on the binary mask and dilates with a 3 x 3 kernel, which cannot be pinned without OpenCV):
+ *   edge0[p]  p is inside and at least one of its 4-neighbours INSIDE THE IMAGE is outside the region -- with per_object != 0
+ *             (d_ids only): has a different id;
+ *   edge[p]   some q with Chebyshev distance <= dilate_iterations from p has edge0[q].
+ * dilate_iterations in 0..HP_SCENE_MAX_DILATE, anything else is HP_ERR_ARG.  One launch; d_out must not alias d_frame.
+ *
+ * hp_scene_overlay: d_out = where the render is set: d_lut_render[render], elsewhere d_lut_input[input], per byte of the
+ * [n_cam][h][w][3] u8 frames.  "Set" = d_mask [n_cam][h][w] != 0 when given, else any channel of the render pixel > 0 (the
+ * reference's get_mask_from_rgb).  The two 256-entry u8 tables (device) hold render * 0.8 + 255 * 0.2 and input * 0.6 + 255 * 0.4
+ * as numpy evaluates and truncates them (happypose_amd.scene.overlay_tables).
+ * n_cam == 0 launches nothing.
+ * ---------------------------------------------------------------------------------- */
+#define HP_SCENE_VIS_FIELDS 10
+#define HP_SCENE_MAX_DILATE 3
+int hp_scene_compose(int n_cam, const int32_t* d_layer_off, int n_layers, int h, int w, const float* d_layer_rgb,
+                     const float* d_layer_nrm, const float* d_layer_depth, float* d_rgb, float* d_nrm, float* d_depth, int32_t* d_ids,
+                     uint8_t* d_mask, void* stream);
+int hp_scene_visibility(int n_cam, const int32_t* d_layer_off, int n_layers, int h, int w, const float* d_layer_depth,
+                        const int32_t* d_ids, int32_t* d_table, void* stream);
+int hp_scene_contour(int n_cam, int h, int w, const uint8_t* d_frame, const uint8_t* d_mask, const int32_t* d_ids, int per_object,
+                     int color_r, int color_g, int color_b, int dilate_iterations, uint8_t* d_out, uint8_t* d_edge, void* stream);
+int hp_scene_overlay(int n_cam, int h, int w, const uint8_t* d_input, const uint8_t* d_render, const uint8_t* d_mask,
+                     const uint8_t* d_lut_render, const uint8_t* d_lut_input, uint8_t* d_out, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -165,6 +165,9 @@ _PROTOS = {
     "hp_scene_contour": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_u8p, c_i32p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_u8p,
                                    c_u8p, C.c_void_p]),
     "hp_scene_overlay": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, c_u8p, C.c_void_p]),
+    "hp_vsd_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "hp_vsd": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_float,
+                         C.c_int, c_f32p, C.c_int, c_i32p, c_i32p, c_f32p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -456,3 +456,205 @@ class PoseErrorMeter:
         if self.report_error_AUC:
             summary.update({"AUC/objects/mean": gt_df.attrs["AUC/objects/mean"], "AUC": gt_df.attrs["AUC"]})
         return summary, {"gt": gt_df, "matches": matches_df, "preds": pred_df, "ap": ap_dfs}
+
+
+# ---- visible-surface discrepancy (BOP's third pose error) ------------------------------------------------------------------------
+BOP_VSD_DELTA = 0.015                                                 # metres
+BOP_VSD_TAUS = tuple(round(0.05 * k, 2) for k in range(1, 11))        # 0.05 ... 0.50, fractions of the diameter
+BOP_VSD_THRESHOLDS = tuple(round(0.05 * k, 2) for k in range(1, 11))  # an estimate is correct when its error is below these
+
+
+def _store_of(renderer):
+    """The ``ops.MeshStore`` of a ``SceneRenderer`` / ``BatchRenderer``, or the store itself."""
+    return renderer if isinstance(renderer, ops.MeshStore) else renderer.store
+
+
+def _distinct_layers(poses: np.ndarray, labels, frames: np.ndarray):
+    """Layer index of every row and the first row of every layer: rows with the same (label, frame, pose bits) share a render."""
+    index, first, layer = {}, [], np.empty(len(labels), dtype=np.int64)
+    for r in range(len(labels)):
+        key = (labels[r], int(frames[r]), poses[r].tobytes())
+        if key not in index:
+            index[key] = len(first)
+            first.append(r)
+        layer[r] = index[key]
+    return layer, np.asarray(first, dtype=np.int64)
+
+
+def vsd(TXO_pred: torch.Tensor, TXO_gt: torch.Tensor, labels, depth: torch.Tensor, K: torch.Tensor, renderer, frame_ids=None,
+        delta: float = BOP_VSD_DELTA, taus=BOP_VSD_TAUS, normalized_by_diameter: bool = True, layer_budget_bytes: Optional[int] = None,
+        return_details: bool = False):
+    """BOP's visible-surface discrepancy (BOP19 visibility rule, ``step`` cost; the definition is in ``include/happypose_amd.h``):
+    ``errors [n, n_tau]`` for the candidate pairs ``(TXO_pred[i], TXO_gt[i])`` of object ``labels[i]`` seen in frame
+    ``frame_ids[i]`` of ``depth [n_frames, H, W]`` (metres, 0 = no measurement) with intrinsics ``K [n_frames, 3, 3]``.
+    ``frame_ids=None``: pair ``i`` belongs to frame ``i``, or every pair to the only frame.
+
+    ``renderer``: a ``SceneRenderer``, a ``BatchRenderer`` or an ``ops.MeshStore``; the diameters are its mesh database's.  The
+    DISTINCT estimated and ground-truth poses (a ground truth shared by several candidates once) are rendered depth-only at the
+    frame's resolution in the single-sample state (``msaa=False, aniso=False, render_rgb=False``), at most
+    ``layer_budget_bytes`` of layers at a time (default: the renderer's, else ``scene.DEFAULT_LAYER_BUDGET_BYTES``), and every chunk is
+    compared by ONE ``hp_vsd`` launch enqueued behind its render: nothing synchronises with the host between the two.
+
+    ``return_details``: also a dict with ``cost`` / ``counts`` (``ops.vsd_tables``) and, for inspection, the rendered
+    ``depth_layers [L, H, W]`` with the ``est_layer`` / ``gt_layer`` / ``frame`` columns that index them."""
+    from .scene import DEFAULT_LAYER_BUDGET_BYTES
+
+    store = _store_of(renderer)
+    dev = store.device
+    labels = np.asarray(labels)
+    n = len(labels)
+    taus = np.asarray(taus, dtype=np.float32).reshape(-1)
+    assert TXO_pred.shape == (n, 4, 4) and TXO_gt.shape == (n, 4, 4), "vsd: one predicted and one ground-truth pose per label"
+    assert depth.dim() == 3 and K.shape == (depth.shape[0], 3, 3), "vsd: depth [n_frames, H, W] and K [n_frames, 3, 3]"
+    n_frames, h, w = depth.shape
+    if frame_ids is None:
+        assert n_frames in (1, n), "vsd: frame_ids is needed unless there is one frame, or one per pair"
+        frames = np.zeros(n, dtype=np.int64) if n_frames == 1 else np.arange(n, dtype=np.int64)
+    else:
+        frames = np.asarray(torch.as_tensor(frame_ids).cpu(), dtype=np.int64)
+        assert frames.shape == (n,) and (n == 0 or (frames.min() >= 0 and frames.max() < n_frames)), "vsd: frame_ids outside depth"
+    depth, K = depth.to(dev, torch.float32).contiguous(), K.to(dev, torch.float32).contiguous()
+    errors = torch.empty((n, len(taus)), dtype=torch.float32, device=dev)
+    details = {"cost": torch.empty((n, len(taus)), dtype=torch.int32, device=dev),
+               "counts": torch.empty((n, ops.VSD_COUNT_FIELDS), dtype=torch.int32, device=dev),
+               "est_layer": np.empty(n, dtype=np.int64), "gt_layer": np.empty(n, dtype=np.int64), "frame": frames}
+    rendered: list = []
+    if n:
+        # the poses decide which renders are shared: they are read on the host once, before anything is enqueued
+        pred_h = np.ascontiguousarray(TXO_pred.detach().to("cpu", torch.float32).numpy())
+        gt_h = np.ascontiguousarray(TXO_gt.detach().to("cpu", torch.float32).numpy())
+        infos = store.mesh_db.infos
+        diameter = np.asarray([infos[label]["diameter_m"] for label in labels], dtype=np.float32)
+        gt_layer, _ = _distinct_layers(gt_h, labels, frames)
+        budget = int(layer_budget_bytes if layer_budget_bytes is not None else getattr(renderer, "layer_budget_bytes", DEFAULT_LAYER_BUDGET_BYTES))
+        max_layers = max(2, budget // (h * w * 4))
+        order = np.argsort(gt_layer, kind="stable")  # the candidates of one ground truth side by side: one render, one chunk
+        key = lambda T, r: (labels[r], int(frames[r]), T[r].tobytes())  # noqa: E731
+        chunks, held = [[]], set()
+        for r in order:  # the longest runs of rows whose distinct renders fit the budget (a row needs both its layers in its chunk)
+            new = {key(pred_h, r), key(gt_h, r)} - held
+            if chunks[-1] and len(held) + len(new) > max_layers:
+                chunks.append([])
+                held, new = set(), {key(pred_h, r), key(gt_h, r)}
+            chunks[-1].append(r)
+            held |= new
+        n_done = 0
+        for rows in chunks:
+            rows = np.asarray(rows, dtype=np.int64)
+            m = len(rows)
+            layer, first = _distinct_layers(np.concatenate([pred_h[rows], gt_h[rows]]), np.concatenate([labels[rows]] * 2),
+                                            np.concatenate([frames[rows]] * 2))
+            poses = np.concatenate([pred_h[rows], gt_h[rows]])[first]
+            l_frames = np.concatenate([frames[rows]] * 2)[first]
+            l_labels = np.concatenate([labels[rows]] * 2)[first]
+            _, _, dep, _ = ops.rasterize(store, store.ids_of(list(l_labels)), torch.as_tensor(poses), K[torch.as_tensor(l_frames, device=dev)],
+                                         (h, w), render_depth=True, render_rgb=False, msaa=False, aniso=False)
+            out = ops.vsd_tables(layer[:m].astype(np.int32), layer[m:].astype(np.int32), frames[rows].astype(np.int32), diameter[rows], depth,
+                                 dep, K, delta, taus, normalized_by_diameter)
+            idx = torch.as_tensor(rows, device=dev)
+            errors[idx] = out["errors"]
+            if return_details:
+                details["cost"][idx], details["counts"][idx] = out["cost"], out["counts"]
+                details["est_layer"][rows], details["gt_layer"][rows] = layer[:m] + n_done, layer[m:] + n_done
+                rendered.append(dep[:, 0])
+            n_done += len(first)
+    if not return_details:
+        return errors
+    details["depth_layers"] = torch.cat(rendered) if rendered else torch.empty((0, h, w), dtype=torch.float32, device=dev)
+    return errors, details
+
+
+def bop_average_recall(ar_vsd: float, ar_mssd: float, ar_mspd: float) -> float:
+    """BOP's score of a method on a dataset: the mean of the three average recalls."""
+    return (float(ar_vsd) + float(ar_mssd) + float(ar_mspd)) / 3.0
+
+
+class VsdMeter:
+    """Average recall under VSD (``AR_VSD`` of the BOP challenge): the fraction of valid ground-truth instances matched by an
+    estimate whose VSD error at misalignment tolerance ``tau`` is below the correctness threshold ``theta``, averaged over all
+    ``(tau, theta)`` of ``taus x correct_ths``.
+
+    ``renderer``: what :func:`vsd` accepts; ``mesh_db`` (a ``MeshDataBase`` or its ``batched()`` tables) names the objects a
+    prediction may carry.  ``targets`` / ``visib_gt_min`` / ``n_top`` select ground truths and predictions as in
+    :class:`PoseErrorMeter`; the matching is its ``get_candidate_matches`` / ``match_poses``, run once per ``(tau, theta)``."""
+
+    def __init__(self, renderer, mesh_db=None, delta: float = BOP_VSD_DELTA, taus=BOP_VSD_TAUS, correct_ths=BOP_VSD_THRESHOLDS,
+                 normalized_by_diameter: bool = True, targets=None, visib_gt_min=-1, n_top=-1, device="cuda"):
+        self.renderer = renderer
+        self.mesh_db = mesh_db
+        self.delta = float(delta)
+        self.taus = tuple(float(t) for t in taus)
+        self.correct_ths = tuple(float(t) for t in correct_ths)
+        assert 1 <= len(self.taus) <= ops.VSD_MAX_TAUS and len(self.correct_ths) >= 1
+        self.normalized_by_diameter = bool(normalized_by_diameter)
+        self.targets = targets
+        self.visib_gt_min = visib_gt_min
+        self.n_top = n_top
+        self.device = device
+        self.reset()
+
+    def reset(self):
+        self.n_gt_valid = 0
+        self.n_matched = np.zeros((len(self.taus), len(self.correct_ths)), dtype=np.int64)
+        self.datas = defaultdict(list)
+
+    def compute_errors(self, TXO_pred, TXO_gt, labels, depth, K, frame_ids) -> np.ndarray:
+        """The one device call of the meter: ``[n, n_tau]`` VSD errors of the candidate pairs."""
+        if len(labels) == 0:
+            return np.empty((0, len(self.taus)), dtype=np.float32)
+        return vsd(TXO_pred, TXO_gt, labels, depth, K, self.renderer, frame_ids=frame_ids, delta=self.delta, taus=self.taus,
+                   normalized_by_diameter=self.normalized_by_diameter).cpu().numpy()
+
+    def add(self, pred_data, gt_data, depth, K, frames=None):
+        """``pred_data`` / ``gt_data``: collections with ``poses [n, 4, 4]`` and ``infos`` (``scene_id``, ``view_id``, ``label``;
+        predictions also ``score``, 1 when absent).  ``depth [n_frames, H, W]`` and ``K [n_frames, 3, 3]`` are the measured
+        frames; ``frames`` lists their ``(scene_id, view_id)`` in that order (default: the views of ``gt_data`` in order of
+        first appearance)."""
+        keys = list(GROUP_KEYS)
+        pred_data, gt_data = pred_data.float(), gt_data.float()
+        if "score" not in pred_data.infos:
+            pred_data.infos["score"] = 1.0
+        if self.mesh_db is not None:
+            unknown = sorted(set(pred_data.infos["label"]) - set(self.mesh_db.infos))
+            assert not unknown, f"VsdMeter: labels {unknown} are not in mesh_db"
+        gt_views = gt_data.infos.loc[:, ["scene_id", "view_id"]].drop_duplicates().reset_index(drop=True)
+        if frames is None:
+            frames = list(zip(gt_views["scene_id"], gt_views["view_id"]))
+        frame_of = {(s, v): i for i, (s, v) in enumerate(frames)}
+        assert len(frame_of) == len(frames) == depth.shape[0] == K.shape[0], "VsdMeter: one distinct (scene_id, view_id) per frame of depth and K"
+        targets = self.targets
+        if targets is not None:
+            targets = gt_views.merge(targets)
+        pred_data.infos["batch_pred_id"] = np.arange(len(pred_data))
+        pred_data = pred_data[gt_views.merge(pred_data.infos)["batch_pred_id"].to_numpy()]
+        pred_data.infos = add_inst_num(pred_data.infos, key="pred_inst_id", group_keys=keys)
+        gt_data.infos = add_inst_num(gt_data.infos, key="gt_inst_id", group_keys=keys)
+        top = get_top_n_ids(pred_data.infos, group_keys=keys, top_key="score", targets=targets, n_top=self.n_top)
+        kept = pred_data.clone()[np.asarray(top, dtype=int)]
+        gt_data.infos = add_valid_gt(gt_data.infos, group_keys=keys, targets=targets, visib_gt_min=self.visib_gt_min)
+        cands = get_candidate_matches(kept.infos, gt_data.infos, group_keys=keys, only_valids=True)
+
+        pred_ids, gt_ids = cands["pred_id"].to_numpy(), cands["gt_id"].to_numpy()
+        frame_ids = np.asarray([frame_of[(s, v)] for s, v in zip(cands["scene_id"], cands["view_id"])], dtype=np.int64)
+        errors = np.asarray(self.compute_errors(kept.poses[pred_ids], gt_data.poses[gt_ids], cands["label"].to_numpy(), depth, K, frame_ids))
+        assert errors.shape == (len(cands), len(self.taus))
+
+        self.n_gt_valid += int(gt_data.infos["valid"].sum())
+        for ti in range(len(self.taus)):
+            cands["error"] = errors[:, ti]
+            for ci, th in enumerate(self.correct_ths):  # BOP: an estimate is correct when its error is BELOW the threshold
+                self.n_matched[ti, ci] += len(match_poses(cands[cands["error"] < th].reset_index(drop=True), group_keys=keys))
+        cands = cands.drop(columns="error")
+        for ti, tau in enumerate(self.taus):
+            cands[f"vsd_{tau:g}"] = errors[:, ti]
+        self.datas["cand_df"].append(cands)
+
+    def summary(self):
+        """``(summary, dfs)``: ``summary["AR_VSD"]`` and the counts; ``dfs["recall"]`` has one row per ``(tau, threshold)`` with
+        ``n_matched`` and ``recall``, ``dfs["cands"]`` every candidate pair with its errors."""
+        recall = self.n_matched / self.n_gt_valid if self.n_gt_valid else np.zeros(self.n_matched.shape)
+        table = pd.DataFrame([{"tau": tau, "threshold": th, "n_matched": int(self.n_matched[ti, ci]), "recall": float(recall[ti, ci])}
+                              for ti, tau in enumerate(self.taus) for ci, th in enumerate(self.correct_ths)])
+        cands = pd.concat(self.datas["cand_df"], ignore_index=True) if self.datas["cand_df"] else pd.DataFrame()
+        summary = {"n_gt_valid": int(self.n_gt_valid), "n_cand": len(cands), "AR_VSD": float(recall.mean())}
+        return summary, {"recall": table, "cands": cands}

@@ -1244,3 +1244,68 @@ def scene_overlay(rgb_input: torch.Tensor, rgb_rendered: torch.Tensor, lut_rende
         check(lib().hp_scene_overlay(n, h, w, ptr(rgb_input), ptr(rgb_rendered), ptr(mask), ptr(lut_render), ptr(lut_input), ptr(out),
                                      stream_ptr(dev)), "hp_scene_overlay")
     return out
+
+
+# ------------------------------------------------------------------------------------------ visible-surface discrepancy (vsd.hip)
+VSD_MAX_TAUS = 16      # HP_VSD_MAX_TAUS
+VSD_COUNT_FIELDS = 4   # HP_VSD_COUNT_FIELDS
+VSD_COUNT_COLUMNS = ("n_union", "n_inter", "n_visib_est", "n_visib_gt")
+
+
+def vsd_workspace_bytes(n_rows: int, h: int, w: int) -> int:
+    """``hp_vsd_workspace_bytes``: rows x blocks of 4096 pixels x 80 bytes."""
+    n = int(lib().hp_vsd_workspace_bytes(int(n_rows), int(h), int(w)))
+    assert n >= 0, "vsd_workspace_bytes: n_rows >= 0, h and w positive, h * w < 2^31"
+    return n
+
+
+def _vsd_ids(ids, n: int, what: str) -> None:
+    """``hp_vsd`` requires ids inside their tables: ids that still live on the host are checked here, before any launch."""
+    t = torch.as_tensor(ids)
+    if t.device.type == "cpu" and t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        assert 0 <= lo and hi < n, f"{what}: ids in [{lo}, {hi}] index a table of {n}"
+
+
+def vsd_tables(est_layer, gt_layer, frame, diameter, depth_test: torch.Tensor, depth_layers: torch.Tensor, K: torch.Tensor,
+               delta: float, taus, normalized_by_diameter: bool = True) -> Dict[str, torch.Tensor]:
+    """``hp_vsd``: row ``r`` compares the depth renders ``depth_layers[est_layer[r]]`` and ``depth_layers[gt_layer[r]]``
+    ([L, H, W] or the rasteriser's [L, 1, H, W], metres, 0 = background) with the measured ``depth_test[frame[r]]`` [F, H, W]
+    under ``K[frame[r]]`` [F, 3, 3]; ``diameter`` [n] in metres.  Returns ``errors`` [n, n_tau] float32 (BOP's VSD, BOP19
+    visibility, step cost), ``cost`` [n, n_tau] int32 (pixels of the intersection at or past every tau) and ``counts``
+    [n, 4] int32 (``VSD_COUNT_COLUMNS``).  One launch pair, no synchronisation."""
+    assert depth_layers.is_cuda and depth_layers.dtype == torch.float32, "depth_layers: float32 on the device"
+    dev = depth_layers.device
+    if depth_layers.dim() == 4:
+        assert depth_layers.shape[1] == 1, "depth_layers: [L, H, W] or [L, 1, H, W]"
+        depth_layers = depth_layers[:, 0]
+    if depth_test.dim() == 4:
+        assert depth_test.shape[1] == 1, "depth_test: [F, H, W] or [F, 1, H, W]"
+        depth_test = depth_test[:, 0]
+    assert depth_layers.dim() == 3 and depth_test.dim() == 3 and depth_test.shape[1:] == depth_layers.shape[1:], "depth_test [F, H, W] and depth_layers [L, H, W]"
+    n_layers, h, w = depth_layers.shape
+    n_frames = depth_test.shape[0]
+    assert K.shape == (n_frames, 3, 3), "vsd: one K per frame"
+    taus = np.ascontiguousarray(np.asarray(taus, dtype=np.float32).reshape(-1))
+    n_tau = len(taus)
+    assert 1 <= n_tau <= VSD_MAX_TAUS, f"vsd: 1 to {VSD_MAX_TAUS} taus"
+    n = len(est_layer)
+    assert len(gt_layer) == len(frame) == len(diameter) == n
+    _vsd_ids(est_layer, n_layers, "vsd: est_layer")
+    _vsd_ids(gt_layer, n_layers, "vsd: gt_layer")
+    _vsd_ids(frame, n_frames, "vsd: frame")
+    est_layer, gt_layer, frame = (_i32(a, dev) for a in (est_layer, gt_layer, frame))
+    diameter = _f32(torch.as_tensor(diameter), dev)
+    depth_test, depth_layers, K = _f32(depth_test, dev), depth_layers.contiguous(), _f32(K, dev)
+    out = {"errors": torch.empty((n, n_tau), dtype=torch.float32, device=dev),
+           "cost": torch.empty((n, n_tau), dtype=torch.int32, device=dev),
+           "counts": torch.empty((n, VSD_COUNT_FIELDS), dtype=torch.int32, device=dev)}
+    if n == 0:
+        return out
+    nbytes = vsd_workspace_bytes(n, h, w)
+    ws = torch.empty(nbytes // 4, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_vsd(n, ptr(est_layer), ptr(gt_layer), ptr(frame), ptr(diameter), ptr(depth_test), n_frames, ptr(depth_layers),
+                           n_layers, ptr(K), h, w, float(delta), n_tau, _np_ptr(taus), 1 if normalized_by_diameter else 0,
+                           ptr(out["counts"]), ptr(out["cost"]), ptr(out["errors"]), ptr(ws), nbytes, stream_ptr(dev)), "hp_vsd")
+    return out

@@ -804,6 +804,47 @@ int hp_scene_contour(int n_cam, int h, int w, const uint8_t* d_frame, const uint
 int hp_scene_overlay(int n_cam, int h, int w, const uint8_t* d_input, const uint8_t* d_render, const uint8_t* d_mask,
                      const uint8_t* d_lut_render, const uint8_t* d_lut_input, uint8_t* d_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * BOP's visible-surface discrepancy (VSD) in its BOP19 form: visibility mode "bop19", cost "step".  The reference leaves it to
+ * bop_toolkit (pose_error.vsd with misc.depth_im_to_dist_im_fast and visibility.estimate_visib_mask_gt / _est); the definition
+ * is restated here in full.  csrc/vsd.hip.
+ *
+ * Row r compares the depth render d_depth_layers[d_est_layer[r]] (the object at the estimated pose) and
+ * d_depth_layers[d_gt_layer[r]] (at the ground-truth pose) with the measured depth image d_depth_test[d_frame[r]] under the
+ * intrinsics d_K[d_frame[r]]; d_diameter[r] is the object's diameter.  All images are [.][h][w] float32 in metres, 0 = no
+ * measurement / background (hp_rasterize's depth output: a pixel is covered iff its centre is); d_K is [n_frames][9]; the three
+ * index columns are int32 [n_rows] and d_diameter float32 [n_rows], on the device.  Many rows may name one layer: a ground-truth
+ * render serves every estimate matched against it.  With D_t, D_e, D_g the three depths of pixel (u, v) (column, row; integer
+ * indices, no half-pixel offset):
+ *   f(u, v) = sqrt(((u - cx) / fx)^2 + ((v - cy) / fy)^2 + 1),   S_x = D_x f   (the distance images)
+ *   V_g = S_g > 0 and (S_g - S_t <= delta or S_t == 0)
+ *   V_e = (S_e > 0 and (S_e - S_t <= delta or S_t == 0)) or (V_g and S_e > 0)
+ *   I = V_g and V_e,  U = V_g or V_e,  n_I = |I|,  n_U = |U|
+ *   c_tau = the number of pixels of I with |S_g - S_e| / d >= tau, d = d_diameter[r] if normalized_by_diameter else 1
+ *   e_tau = (c_tau + n_U - n_I) / n_U, and 1 when n_U == 0.
+ * f and the S_x are float32 (one f per pixel, applied to the three depths); a pixel within a few float32 roundings of a threshold
+ * may fall on either side of it.  Everything accumulated is an integer.
+ * Outputs: d_counts [n_rows][HP_VSD_COUNT_FIELDS] int32 = n_U, n_I, |V_e|, |V_g|; d_cost [n_rows][n_tau] int32 = c_tau; d_errors
+ * [n_rows][n_tau] float32 = e_tau, the integer quotient rounded once.  taus is a HOST array of n_tau values,
+ * 1 <= n_tau <= HP_VSD_MAX_TAUS; d_diameter may be NULL without normalized_by_diameter and must be positive with it.
+ * The ids in the three index columns MUST be in range (0 <= layer < n_layers, 0 <= frame < n_frames): the caller checks them
+ * where they still live on the host.  The kernels do compare them with the table sizes: a row with an id outside reads no image
+ * and is answered with -1 in its counts and cost and NaN in its errors.
+ * One pass over the pixels, a workgroup per (row, block of 4096 pixels), 16-byte loads when h * w is a multiple of 4 and the
+ * image buffers are 16-byte aligned; every workgroup leaves one record of integers in d_workspace
+ * (hp_vsd_workspace_bytes(n_rows, h, w) bytes: n_rows x ceil(h w / 4096) x 80), added per row in block order by a second launch.
+ * No atomics: a row's outputs do not depend on the other rows of the call, on their order or on the run.
+ * n_rows == 0 returns HP_OK after the scalar checks and launches nothing; h * w < 2^31 and at most 65535 pixel blocks per
+ * frame.  hp_vsd_workspace_bytes returns -1 for a negative n_rows or a frame outside those limits.
+ * ---------------------------------------------------------------------------------- */
+#define HP_VSD_MAX_TAUS 16
+#define HP_VSD_COUNT_FIELDS 4
+int64_t hp_vsd_workspace_bytes(int n_rows, int h, int w);
+int hp_vsd(int n_rows, const int32_t* d_est_layer, const int32_t* d_gt_layer, const int32_t* d_frame, const float* d_diameter,
+           const float* d_depth_test, int n_frames, const float* d_depth_layers, int n_layers, const float* d_K, int h, int w,
+           float delta, int n_tau, const float* taus, int normalized_by_diameter, int32_t* d_counts, int32_t* d_cost,
+           float* d_errors, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

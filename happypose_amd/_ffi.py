@@ -168,6 +168,12 @@ _PROTOS = {
     "hp_vsd_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
     "hp_vsd": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_f32p, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, C.c_int, C.c_float,
                          C.c_int, c_f32p, C.c_int, c_i32p, c_i32p, c_f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_mask_pack_words": (C.c_int64, [C.c_int, C.c_int]),
+    "hp_mask_pack": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, C.c_void_p, c_i32p, C.c_void_p]),
+    "hp_det_iou": (C.c_int, [C.c_int, c_i32p, c_i32p, C.c_int, C.c_int, c_f32p, c_f32p, C.c_void_p, c_i32p, C.c_void_p, c_i32p, C.c_int,
+                             c_f32p, c_i32p, c_i32p, c_f32p, C.c_void_p]),
+    "hp_det_match": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, C.c_int64, C.c_int64, C.c_int64, c_u8p, c_f32p,
+                               C.c_int, c_i32p, c_u8p, c_i32p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

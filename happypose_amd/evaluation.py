@@ -25,6 +25,7 @@ import pandas as pd
 import torch
 
 from . import ops
+from .tensor_collection import PandasTensorCollection
 
 GROUP_KEYS = ("scene_id", "view_id", "label")
 ERROR_TYPES = ("ADD", "ADD-S", "ADD(-S)", "ADD-SYM", "MSSD", "MSPD")
@@ -209,7 +210,7 @@ def average_precision(y_true, y_score) -> float:
 
 # ---- the meter -------------------------------------------------------------------------------------------------------------------
 _FILL = {"norm": np.inf, "0.1d": False, "xyz": np.inf, "TCO_xyz": np.inf, "TCO_norm": np.inf, "obj_diameter": np.nan,
-         "TXO_pred": np.nan, "score": np.nan}
+         "TXO_pred": np.nan, "score": np.nan, "iou": np.nan, "iou_valid": False}
 _ARRAY_COLUMNS = {"xyz": (3,), "TCO_xyz": (3,), "TXO_pred": (4, 4)}
 
 
@@ -658,3 +659,378 @@ class VsdMeter:
         cands = pd.concat(self.datas["cand_df"], ignore_index=True) if self.datas["cand_df"] else pd.DataFrame()
         summary = {"n_gt_valid": int(self.n_gt_valid), "n_cand": len(cands), "AR_VSD": float(recall.mean())}
         return summary, {"recall": table, "cands": cands}
+
+
+# ---- detections and instance masks (CP/evaluation/meters/detection_meters.py; COCO average precision) ----------------------------
+# The IoU definitions and the matching rule are restated in include/happypose_amd.h (csrc/det_eval.hip).  CocoMeter is the PUBLISHED
+# definition of COCO's average precision (pycocotools 2.0: COCOeval.evaluateImg / accumulate / summarize, without area ranges and
+# crowd regions) restated here: pycocotools is not a dependency, so nothing below could be pinned against it.
+COCO_IOU_THRESHOLDS = tuple(round(0.5 + 0.05 * k, 2) for k in range(10))  # 0.50 : 0.05 : 0.95
+COCO_RECALL_POINTS = np.linspace(0.0, 1.0, 101)
+
+
+def _all_pairs(n1: int, n2: int):
+    return np.repeat(np.arange(n1, dtype=np.int32), n2), np.tile(np.arange(n2, dtype=np.int32), n1)
+
+
+def box_iou(boxes1: torch.Tensor, boxes2: torch.Tensor) -> torch.Tensor:
+    """``torchvision.ops.box_iou``: ``[n1, n2]`` IoU of xyxy boxes on the device (0 / 0 is NaN, as there)."""
+    n1, n2 = boxes1.shape[0], boxes2.shape[0]
+    if n1 * n2 == 0:
+        return torch.empty((n1, n2), dtype=torch.float32, device=boxes1.device)
+    i, j = _all_pairs(n1, n2)
+    return ops.det_iou(i, j, boxes_pred=boxes1, boxes_gt=boxes2)["box_iou"].reshape(n1, n2)
+
+
+def mask_iou(masks1: torch.Tensor, masks2: torch.Tensor) -> torch.Tensor:
+    """``[n1, n2]`` IoU of ``[n, H, W]`` bool / uint8 masks on the device; 0 where both masks are empty.  Each mask is bit-packed
+    once; no ``[n1, n2, H, W]`` temporary exists."""
+    n1, n2 = masks1.shape[0], masks2.shape[0]
+    assert masks1.shape[1:] == masks2.shape[1:], "mask_iou: one resolution"
+    if n1 * n2 == 0:
+        return torch.empty((n1, n2), dtype=torch.float32, device=masks1.device)
+    i, j = _all_pairs(n1, n2)
+    return ops.det_iou(i, j, packed_pred=ops.mask_pack(masks1), packed_gt=ops.mask_pack(masks2))["mask_iou"].reshape(n1, n2)
+
+
+def plan_detection_rows(pred_infos: pd.DataFrame, gt_infos: pd.DataFrame, max_dets: Optional[int] = None, group_keys=GROUP_KEYS):
+    """The rows of a detection evaluation, on the host alone.  A group is one value of ``group_keys`` present in either frame
+    (groups in sorted key order).  Inside a group the detections are ordered by descending ``score`` (stable: equal scores keep
+    their row order) and capped at ``max_dets``; the ground truths by ``ignore`` (column of ``gt_infos``, all False when absent),
+    the non-ignored ones first, stable.  Returns a dict:
+
+    ``groups``     DataFrame: the keys, ``n_det``, ``n_gt`` and the starts ``row_off`` / ``det_off`` / ``gt_off`` of every group;
+    ``det_order``  row positions in ``pred_infos`` of the kept detections, group after group, with ``det_group`` (their group);
+    ``gt_order``   row positions in ``gt_infos`` likewise, with ``gt_group`` and ``gt_ignore``;
+    ``pred_idx`` / ``gt_idx``  the rows for ``ops.det_iou``: every group's ``n_det x n_gt`` pairs, detection-major, as row positions
+                   in the two frames -- what ``ops.det_match`` expects as its dense matrices."""
+    keys = list(group_keys)
+    score = pred_infos["score"].to_numpy(dtype=float) if len(pred_infos) else np.zeros(0)
+    ignore = gt_infos["ignore"].to_numpy(dtype=bool) if "ignore" in gt_infos else np.zeros(len(gt_infos), dtype=bool)
+    members: Dict[tuple, list] = {}
+    for side, infos in enumerate((pred_infos, gt_infos)):
+        cols = [infos[k].tolist() for k in keys] if len(infos) else [[] for _ in keys]
+        for row, key in enumerate(zip(*cols)):
+            members.setdefault(key, ([], []))[side].append(row)
+    table, det_order, gt_order, det_group, gt_group, pred_idx, gt_idx = [], [], [], [], [], [], []
+    row_off = det_off = gt_off = 0
+    for g, key in enumerate(sorted(members)):
+        dets, gts = (np.asarray(m, dtype=np.int64) for m in members[key])
+        dets = dets[np.argsort(-score[dets], kind="mergesort")]
+        if max_dets is not None:
+            dets = dets[:max_dets]
+        gts = gts[np.argsort(ignore[gts], kind="mergesort")]
+        table.append((*key, len(dets), len(gts), row_off, det_off, gt_off))
+        det_order.append(dets), gt_order.append(gts)
+        det_group.append(np.full(len(dets), g)), gt_group.append(np.full(len(gts), g))
+        pred_idx.append(np.repeat(dets, len(gts))), gt_idx.append(np.tile(gts, len(dets)))
+        row_off, det_off, gt_off = row_off + len(dets) * len(gts), det_off + len(dets), gt_off + len(gts)
+    cat = lambda parts: np.concatenate(parts).astype(np.int64) if parts else np.zeros(0, dtype=np.int64)  # noqa: E731
+    gt_order = cat(gt_order)
+    return {"groups": pd.DataFrame(table, columns=[*keys, "n_det", "n_gt", "row_off", "det_off", "gt_off"]),
+            "det_order": cat(det_order), "det_group": cat(det_group), "gt_order": gt_order, "gt_group": cat(gt_group),
+            "gt_ignore": ignore[gt_order], "pred_idx": cat(pred_idx), "gt_idx": cat(gt_idx)}
+
+
+def _device_iou(iou_type: str, plan, pred_data, gt_data) -> Dict[str, torch.Tensor]:
+    """The one ``hp_det_iou`` launch of an ``add`` call: the plan's rows on the boxes (``bbox``) or on the masks, packed once
+    each (``segm``)."""
+    if iou_type == "bbox":
+        return ops.det_iou(plan["pred_idx"], plan["gt_idx"], boxes_pred=pred_data.bboxes.float(), boxes_gt=gt_data.bboxes.float())
+    return ops.det_iou(plan["pred_idx"], plan["gt_idx"], packed_pred=ops.mask_pack(pred_data.masks), packed_gt=ops.mask_pack(gt_data.masks))
+
+
+def _check_iou_type(iou_type: str) -> str:
+    if iou_type not in ("bbox", "segm"):
+        raise ValueError("iou_type must be 'bbox' or 'segm'", iou_type)
+    return iou_type
+
+
+class DetectionMeter:
+    """The reference's ``DetectionMeter`` with its constructor arguments, plus ``iou_type``: ``"bbox"`` scores ``bboxes [n, 4]``
+    (xyxy) with torchvision's ``box_iou``, ``"segm"`` scores ``masks [n, H, W]`` (bool) with the mask IoU.  ``add`` and ``summary``
+    follow the reference step by step; every candidate pair of an ``add`` call goes through ONE ``hp_det_iou`` launch, so
+    ``errors_bsz`` is kept for compatibility and ignored.  ``summary()`` returns the reference's keys and pandas frames instead
+    of xarray datasets, like :class:`PoseErrorMeter`."""
+
+    def __init__(self, iou_threshold=0.5, errors_bsz=512, consider_all_predictions=False, targets=None, visib_gt_min=-1, n_top=-1,
+                 iou_type="bbox"):
+        self.iou_threshold = iou_threshold
+        self.consider_all_predictions = consider_all_predictions
+        self.targets = targets
+        self.visib_gt_min = visib_gt_min
+        self.errors_bsz = errors_bsz
+        self.n_top = n_top
+        self.iou_type = _check_iou_type(iou_type)
+        self.reset()
+
+    def reset(self):
+        self.datas = defaultdict(list)
+
+    def add(self, pred_data, gt_data):
+        keys = list(GROUP_KEYS)
+        # predictions of the scenes and views the ground truth covers
+        gt_views = gt_data.infos.loc[:, ["scene_id", "view_id"]].drop_duplicates().reset_index(drop=True)
+        targets = self.targets
+        if targets is not None:
+            targets = gt_views.merge(targets)
+        pred_data.infos["batch_pred_id"] = np.arange(len(pred_data))
+        pred_data = pred_data[gt_views.merge(pred_data.infos)["batch_pred_id"].to_numpy()]
+
+        pred_data.infos = add_inst_num(pred_data.infos, key="pred_inst_id", group_keys=keys)
+        gt_data.infos = add_inst_num(gt_data.infos, key="gt_inst_id", group_keys=keys)
+
+        # BOP: the best n predictions of a group
+        if not self.consider_all_predictions:
+            top = get_top_n_ids(pred_data.infos, group_keys=keys, top_key="score", targets=targets, n_top=self.n_top)
+            kept = pred_data.clone()[np.asarray(top, dtype=int)]
+        else:
+            kept = pred_data.clone()
+
+        gt_data.infos = add_valid_gt(gt_data.infos, group_keys=keys, targets=targets, visib_gt_min=self.visib_gt_min)
+        cands = get_candidate_matches(kept.infos, gt_data.infos, group_keys=keys, only_valids=True)
+
+        # the candidates are the rows of the plan over the valid ground truths: one launch, rows sorted by group
+        valid_rows = np.where(gt_data.infos["valid"].to_numpy(dtype=bool))[0]
+        plan = plan_detection_rows(kept.infos, gt_data.infos.iloc[valid_rows].drop(columns="ignore", errors="ignore"), group_keys=keys)
+        plan["gt_idx"] = valid_rows[plan["gt_idx"]]
+        out = _device_iou(self.iou_type, plan, kept, gt_data)
+        iou_rows = out["box_iou" if self.iou_type == "bbox" else "mask_iou"].cpu().numpy().astype(np.float64)
+        n_gt_rows = max(len(gt_data.infos), 1)
+        pair = plan["pred_idx"] * n_gt_rows + plan["gt_idx"]
+        sorter = np.argsort(pair, kind="stable")
+        want = cands["pred_id"].to_numpy(dtype=np.int64) * n_gt_rows + cands["gt_id"].to_numpy(dtype=np.int64)
+        assert len(want) == len(pair) and np.array_equal(pair[sorter], np.sort(want)), "plan and candidates name different pairs"
+        ious = iou_rows[sorter[np.searchsorted(pair[sorter], want)]] if len(want) else np.zeros(0)
+
+        # matches can only be candidates within the threshold
+        cands["iou"] = ious
+        cands = cands[cands["iou"] >= self.iou_threshold].reset_index(drop=True)
+        cands["error"] = -cands["iou"]
+        matches = match_poses(cands, group_keys=keys)
+
+        gt_keys = [*keys, "gt_inst_id", "valid"] + (["visib_fract"] if "visib_fract" in gt_views else [])
+        gt = gt_data.infos.loc[:, gt_keys].reset_index(drop=True)
+        preds = pred_data.infos.loc[:, [*keys, "pred_inst_id", "score"]].reset_index(drop=True)
+        matches = matches.loc[:, [*keys, "pred_inst_id", "gt_inst_id", "cand_id"]].reset_index(drop=True)
+        match_iou = ious[matches["cand_id"].to_numpy(dtype=int)]
+        matches["iou"] = match_iou
+        matches["iou_valid"] = match_iou >= self.iou_threshold
+
+        matches = _left_join(matches, preds, [*keys, "pred_inst_id"])
+        gt = _left_join(gt, matches, [*keys, "gt_inst_id"])
+        preds["iou_valid"] = _left_join(preds, matches, [*keys, "pred_inst_id"])["iou_valid"].to_numpy()
+
+        self.datas["gt_df"].append(gt)
+        self.datas["pred_df"].append(preds)
+        self.datas["matches_df"].append(matches)
+
+    def summary(self):
+        gt_df = pd.concat(self.datas["gt_df"], ignore_index=True)
+        matches_df = pd.concat(self.datas["matches_df"], ignore_index=True)
+        pred_df = pd.concat(self.datas["pred_df"], ignore_index=True)
+        valid_df = gt_df[gt_df["valid"].to_numpy(dtype=bool)]
+
+        # AP / mAP at the IoU threshold
+        valid_k = "iou_valid"
+        keys = list(GROUP_KEYS)
+        if self.n_top > 0:
+            per_group = gt_df[[*keys, "valid"]].groupby(keys).sum().reset_index()
+            per_group["gt_count"] = np.minimum(self.n_top, per_group["valid"])
+            n_gts = {label: group["gt_count"].sum() for label, group in per_group.groupby("label")}
+        else:
+            n_gts = gt_df[["label", "valid"]].groupby("label")["valid"].sum().to_dict()
+
+        def compute_ap(label_df, label_n_gt):
+            label_df = label_df.sort_values("score", ascending=False).reset_index(drop=True)
+            label_df["n_tp"] = np.cumsum(label_df[valid_k].to_numpy().astype(float))
+            label_df["prec"] = label_df["n_tp"] / (np.arange(len(label_df)) + 1)
+            label_df["recall"] = label_df["n_tp"] / label_n_gt
+            y_true = label_df[valid_k].to_numpy(dtype=bool)
+            ap = average_precision(y_true, label_df["score"]) * y_true.sum() / label_n_gt
+            label_df["AP"] = ap
+            label_df["n_gt"] = label_n_gt
+            return ap, label_df
+
+        ap_dfs = {}
+        df = pred_df[["label", valid_k, "score"]].set_index("label")
+        for label, label_n_gt in n_gts.items():
+            if label in df.index:  # the reference's `df.index.contains(label)`, which pandas removed in 1.0
+                label_df = df.loc[[label]]
+                if label_df[valid_k].sum() > 0:
+                    _, ap_dfs[label] = compute_ap(label_df, label_n_gt)
+        if ap_dfs:
+            mAP = np.mean([np.unique(ap_df["AP"]).item() for ap_df in ap_dfs.values()])
+            AP, ap_dfs["all"] = compute_ap(df.reset_index(), sum(n_gts.values()))
+        else:
+            AP, mAP = 0.0, 0.0
+        n_gt_valid = int(sum(n_gts.values()))
+
+        summary = {
+            "n_gt": len(gt_df),
+            "n_gt_valid": n_gt_valid,
+            "n_pred": len(pred_df),
+            "n_matched": len(matches_df),
+            "matched_gt_ratio": len(matches_df) / n_gt_valid,
+            "pred_matched_ratio": len(pred_df) / max(len(matches_df), 1),
+            "iou_valid_recall": float(valid_df[valid_k].sum()) / n_gt_valid,
+            "AP": AP,
+            "mAP": mAP,
+        }
+        return summary, {"gt": gt_df, "matches": matches_df, "preds": pred_df, "ap": ap_dfs}
+
+
+def coco_accumulate(det_label, det_score, det_match, det_ignore, gt_label, gt_ignore, iou_thresholds=COCO_IOU_THRESHOLDS):
+    """COCO's ``accumulate`` and ``summarize`` on match tables, in numpy float64.  ``det_match`` / ``det_ignore`` are
+    ``[n_thr, n_det]`` (match >= 0: matched), the other arguments one entry per detection / ground truth; detections are taken in
+    the order given (frame after frame).  Per (label, threshold): sort by descending score (mergesort), cumulative true and false
+    positives without the ignored detections, ``recall = tp / n_gt_not_ignored``, ``precision = tp / (tp + fp + eps)`` made
+    monotone from the right and sampled at the 101 recall points with ``searchsorted(side="left")``.  A label without a
+    non-ignored ground truth is left out.  Returns ``(summary, per_label)``: ``AP`` (mean over labels, thresholds and recall
+    points), ``AP50`` / ``AP75`` (-1 when the threshold is not evaluated), ``AR`` (mean final recall), -1 throughout when no label
+    counts; ``per_label`` has one row per counted label."""
+    thr = np.asarray(iou_thresholds, dtype=np.float64).reshape(-1)
+    det_label, gt_label = np.asarray(det_label, dtype=object), np.asarray(gt_label, dtype=object)
+    det_score = np.asarray(det_score, dtype=np.float64)
+    matched = np.asarray(det_match).reshape(len(thr), -1) >= 0
+    det_ignore = np.asarray(det_ignore, dtype=bool).reshape(len(thr), -1)
+    gt_ignore = np.asarray(gt_ignore, dtype=bool)
+    eps = np.spacing(1.0)
+    rows, precisions, recalls = [], [], []
+    for label in sorted(set(gt_label.tolist())):
+        n_gt = int(np.sum((gt_label == label) & ~gt_ignore))
+        if n_gt == 0:
+            continue
+        of_label = np.where(det_label == label)[0]
+        order = of_label[np.argsort(-det_score[of_label], kind="mergesort")]
+        tps, fps = matched[:, order] & ~det_ignore[:, order], ~matched[:, order] & ~det_ignore[:, order]
+        tp_sum, fp_sum = np.cumsum(tps, axis=1).astype(np.float64), np.cumsum(fps, axis=1).astype(np.float64)
+        precision, recall = np.zeros((len(thr), len(COCO_RECALL_POINTS))), np.zeros(len(thr))
+        for t in range(len(thr)):
+            tp, fp = tp_sum[t], fp_sum[t]
+            if len(tp) == 0:
+                continue
+            rc = tp / n_gt
+            pr = tp / (fp + tp + eps)
+            recall[t] = rc[-1]
+            pr = np.maximum.accumulate(pr[::-1])[::-1]
+            at = np.searchsorted(rc, COCO_RECALL_POINTS, side="left")
+            inside = at < len(pr)
+            precision[t, inside] = pr[at[inside]]
+        precisions.append(precision), recalls.append(recall)
+        rows.append({"label": label, "n_gt": n_gt, "n_det": len(order), "AP": float(precision.mean()), "AR": float(recall.mean())})
+    if not rows:
+        nothing = {"AP": -1.0, "AP50": -1.0, "AP75": -1.0, "AR": -1.0}
+        return nothing, pd.DataFrame(rows, columns=["label", "n_gt", "n_det", "AP", "AR"])
+    precisions, recalls = np.stack(precisions), np.stack(recalls)  # [labels, thr, 101], [labels, thr]
+
+    def at_threshold(value):
+        t = np.where(np.isclose(thr, value))[0]
+        return float(precisions[:, t[0]].mean()) if len(t) else -1.0
+
+    per_label = pd.DataFrame(rows)
+    for name, value in (("AP50", 0.5), ("AP75", 0.75)):
+        t = np.where(np.isclose(thr, value))[0]
+        per_label[name] = precisions[:, t[0]].mean(axis=1) if len(t) else -1.0
+    return {"AP": float(precisions.mean()), "AP50": at_threshold(0.5), "AP75": at_threshold(0.75), "AR": float(recalls.mean())}, per_label
+
+
+class CocoMeter:
+    """BOP's score of its 2D detection (``iou_type="bbox"``) and 2D segmentation (``"segm"``) tasks: COCO average precision over
+    ``iou_thresholds``, at most ``max_dets`` detections per frame and label.  This is the PUBLISHED definition (pycocotools 2.0
+    without area ranges and crowd regions) restated here -- pycocotools is not a dependency and nothing was pinned against it.
+
+    ``add(pred_data, gt_data)`` reads ``infos`` (``scene_id``, ``view_id``, ``label``; ``score`` on predictions) and ``bboxes
+    [n, 4]`` xyxy or ``masks [n, H, W]`` bool.  A ground truth is ignored when its ``ignore`` column is set, or when
+    ``visib_gt_min`` is given and its ``visib_fract`` is below it; BOP's own visibility cut-off is NOT built in -- pass it.  Every
+    prediction counts, also on a frame without ground truth.  ``add`` packs the masks, scores all pairs of a frame and label in one
+    ``hp_det_iou`` launch and matches them in one ``hp_det_match`` launch; only the match tables come to the host.
+    ``summary()`` is :func:`coco_accumulate` over everything added: ``AP``, ``AP50``, ``AP75``, ``AR`` (recall at ``max_dets``)
+    and the frames ``labels`` (per label), ``dets`` and ``gts`` (the match tables, one ``match_<thr>`` column per threshold)."""
+
+    def __init__(self, iou_type="bbox", iou_thresholds=COCO_IOU_THRESHOLDS, max_dets=100, visib_gt_min=None):
+        self.iou_type = _check_iou_type(iou_type)
+        self.iou_thresholds = tuple(float(t) for t in iou_thresholds)
+        assert len(self.iou_thresholds) >= 1
+        self.max_dets = int(max_dets)
+        self.visib_gt_min = visib_gt_min
+        self.reset()
+
+    def reset(self):
+        self.datas = defaultdict(list)
+
+    def add(self, pred_data, gt_data):
+        keys = list(GROUP_KEYS)
+        pred_infos, gt_infos = pred_data.infos.reset_index(drop=True), gt_data.infos.reset_index(drop=True).copy()
+        ignore = gt_infos["ignore"].to_numpy(dtype=bool) if "ignore" in gt_infos else np.zeros(len(gt_infos), dtype=bool)
+        if self.visib_gt_min is not None:
+            ignore = ignore | (gt_infos["visib_fract"].to_numpy(dtype=float) < self.visib_gt_min)
+        gt_infos["ignore"] = ignore
+        plan = plan_detection_rows(pred_infos, gt_infos, max_dets=self.max_dets, group_keys=keys)
+        n_thr = len(self.iou_thresholds)
+        if len(plan["pred_idx"]):
+            out = _device_iou(self.iou_type, plan, pred_data, gt_data)
+            iou = out["box_iou" if self.iou_type == "bbox" else "mask_iou"]
+            tables = ops.det_match(iou, plan["groups"]["n_det"].to_numpy(), plan["groups"]["n_gt"].to_numpy(), plan["gt_ignore"],
+                                   self.iou_thresholds)
+            tables = {k: v.cpu().numpy() for k, v in tables.items()}
+        else:  # nothing to compare: every detection is unmatched
+            tables = {"det_match": np.full((n_thr, len(plan["det_order"])), -1, dtype=np.int32),
+                      "det_ignore": np.zeros((n_thr, len(plan["det_order"])), dtype=bool),
+                      "gt_match": np.full((n_thr, len(plan["gt_order"])), -1, dtype=np.int32)}
+        dets = pred_infos.iloc[plan["det_order"]][[*keys, "score"]].reset_index(drop=True)
+        gts = gt_infos.iloc[plan["gt_order"]][[*keys, "ignore"]].reset_index(drop=True)
+        self.datas["dets"].append(dets), self.datas["gts"].append(gts)
+        for k, v in tables.items():
+            self.datas[k].append(v)
+
+    def summary(self):
+        keys = list(GROUP_KEYS)
+        dets = pd.concat(self.datas["dets"], ignore_index=True) if self.datas["dets"] else pd.DataFrame(columns=[*keys, "score"])
+        gts = pd.concat(self.datas["gts"], ignore_index=True) if self.datas["gts"] else pd.DataFrame(columns=[*keys, "ignore"])
+        n_thr = len(self.iou_thresholds)
+        cat = lambda k, dtype: np.concatenate(self.datas[k], axis=1) if self.datas[k] else np.zeros((n_thr, 0), dtype=dtype)  # noqa: E731
+        det_match, det_ignore, gt_match = cat("det_match", np.int32), cat("det_ignore", bool), cat("gt_match", np.int32)
+        summary, per_label = coco_accumulate(dets["label"].to_numpy(), dets["score"].to_numpy(), det_match, det_ignore,
+                                             gts["label"].to_numpy(), gts["ignore"].to_numpy(), self.iou_thresholds)
+        for t, thr in enumerate(self.iou_thresholds):
+            dets[f"match_{thr:g}"], dets[f"ignore_{thr:g}"], gts[f"match_{thr:g}"] = det_match[t], det_ignore[t], gt_match[t]
+        summary.update({"n_pred": len(dets), "n_gt": len(gts), "n_gt_not_ignored": int((~gts["ignore"].to_numpy(dtype=bool)).sum())})
+        return summary, {"labels": per_label, "dets": dets, "gts": gts}
+
+
+def bop_box_to_xyxy(boxes) -> np.ndarray:
+    """BOP's inclusive ``(x, y, w, h)`` (the box covers pixels ``x .. x + w - 1``) as the xyxy box ``(x, y, x + w, y + h)`` of the
+    pixel AREA, whose width is ``w``: what ``box_iou`` measures."""
+    b = np.asarray(boxes, dtype=np.float32).reshape(-1, 4)
+    return np.stack([b[:, 0], b[:, 1], b[:, 0] + b[:, 2], b[:, 1] + b[:, 3]], axis=1)
+
+
+def scene_ground_truth(scene_renderer, object_datas, camera_datas, frames) -> PandasTensorCollection:
+    """Ground-truth detections of a rendered scene, for datasets without mask files: one row per (camera, object) with at least
+    one visible pixel.  ``frames`` lists the ``(scene_id, view_id)`` of every camera.  ``masks`` [n, H, W] bool are the pixels the
+    object wins in its camera's composed id map, ``bboxes`` [n, 4] the xyxy form of BOP's ``bbox_visib``, and ``infos`` carries
+    ``scene_id``, ``view_id``, ``label``, ``cam_id``, ``obj_id``, ``px_count_all``, ``px_count_visib`` and ``visib_fract``.  All
+    cameras must share one resolution.  Built on ``render_scene_tensors`` and ``ops.scene_visibility``."""
+    from .scene import _object_data
+
+    objects = [_object_data(o) for o in object_datas]
+    assert len(frames) == len(camera_datas), "scene_ground_truth: one (scene_id, view_id) per camera"
+    groups = scene_renderer.render_scene_tensors(objects, camera_datas, [], render_depth=True, keep_layer_depth=True)
+    assert len(groups) == 1, "scene_ground_truth: the cameras must share one resolution"
+    (g,) = groups
+    table = ops.scene_visibility(g["layer_off"], g["layer_depth"], g["ids"]).cpu().numpy()
+    n_obj = len(objects)
+    layer_object = g["layer_object"].cpu().numpy()
+    local_cam = np.repeat(np.arange(len(g["cameras"])), n_obj)
+    keep = np.where(table[:, 1] > 0)[0]
+    dev = g["ids"].device
+    masks = g["ids"][torch.as_tensor(local_cam[keep], device=dev)] == torch.as_tensor(layer_object[keep], device=dev, dtype=torch.int32)[:, None, None]
+    t = table[keep]
+    boxes = bop_box_to_xyxy(np.stack([t[:, 6], t[:, 7], t[:, 8] - t[:, 6] + 1, t[:, 9] - t[:, 7] + 1], axis=1)) if len(keep) else np.zeros((0, 4), np.float32)
+    cams = [g["cameras"][c] for c in local_cam[keep]]
+    infos = pd.DataFrame({"scene_id": [frames[c][0] for c in cams], "view_id": [frames[c][1] for c in cams],
+                          "label": [objects[j].label for j in layer_object[keep]], "cam_id": cams, "obj_id": layer_object[keep].astype(int),
+                          "px_count_all": t[:, 0].astype(int), "px_count_visib": t[:, 1].astype(int),
+                          "visib_fract": t[:, 1] / np.maximum(t[:, 0], 1)})
+    return PandasTensorCollection(infos, masks=masks, bboxes=torch.as_tensor(boxes, device=dev))

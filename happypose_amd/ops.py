@@ -1309,3 +1309,124 @@ def vsd_tables(est_layer, gt_layer, frame, diameter, depth_test: torch.Tensor, d
                            n_layers, ptr(K), h, w, float(delta), n_tau, _np_ptr(taus), 1 if normalized_by_diameter else 0,
                            ptr(out["counts"]), ptr(out["cost"]), ptr(out["errors"]), ptr(ws), nbytes, stream_ptr(dev)), "hp_vsd")
     return out
+
+
+# ------------------------------------------------------------------------------------ detection and mask scoring (det_eval.hip)
+MASK_MAX_PIXELS = 1 << 24  # hp_mask_pack: every pixel count is exact in float32
+
+
+def mask_pack_words(h: int, w: int) -> int:
+    """``hp_mask_pack_words``: ``ceil(h * w / 64)``."""
+    n = int(lib().hp_mask_pack_words(int(h), int(w)))
+    assert n >= 0, f"mask_pack_words: h and w positive, h * w <= {MASK_MAX_PIXELS}"
+    return n
+
+
+def mask_pack(masks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``hp_mask_pack``: ``masks`` [n, H, W] bool / uint8 on the device (non-zero = set) -> ``words`` [n, ceil(H W / 64)] int64
+    (the uint64 words bit for bit: bit ``i`` of word ``k`` is pixel ``64 k + i``, the tail bits of the last word are 0) and ``area``
+    [n] int32.  A view whose planes are dense is packed where it lies, whatever its base address."""
+    assert masks.dim() == 3 and masks.dtype in (torch.bool, torch.uint8) and masks.is_cuda, "masks: [n, H, W] bool / uint8 on the device"
+    n, h, w = masks.shape
+    dev = masks.device
+    masks = masks.contiguous().view(torch.uint8)
+    words = torch.empty((n, mask_pack_words(h, w)), dtype=torch.int64, device=dev)
+    area = torch.empty((n,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_mask_pack(n, h, w, ptr(masks), ptr(words), ptr(area), stream_ptr(dev)), "hp_mask_pack")
+    return words, area
+
+
+def _det_ids(ids, n: int, what: str) -> None:
+    """The kernels require ids inside their tables: ids that still live on the host are checked here, before any launch."""
+    t = torch.as_tensor(ids)
+    if t.device.type == "cpu" and t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        assert 0 <= lo and hi < n, f"{what}: ids in [{lo}, {hi}] index a table of {n}"
+
+
+def _packed(p, what: str):
+    words, area = p
+    assert words.dim() == 2 and words.dtype == torch.int64 and words.is_cuda and words.shape[1] >= 1, f"{what}: words [n, W64] int64 on the device"
+    assert area.shape == (words.shape[0],) and area.dtype == torch.int32 and area.device == words.device, f"{what}: area [n] int32"
+    return words.contiguous(), area.contiguous()
+
+
+def det_iou(pred_idx, gt_idx, boxes_pred: Optional[torch.Tensor] = None, boxes_gt: Optional[torch.Tensor] = None,
+            packed_pred=None, packed_gt=None) -> Dict[str, Optional[torch.Tensor]]:
+    """``hp_det_iou``: row ``r`` compares prediction ``pred_idx[r]`` with ground truth ``gt_idx[r]``.  ``boxes_*`` [n, 4] xyxy
+    give ``box_iou`` [n_rows] float32 (torchvision's ``box_iou``; 0 / 0 is NaN); ``packed_*`` = ``mask_pack(...)`` give ``inter`` /
+    ``union`` [n_rows] int32 and ``mask_iou`` [n_rows] float32 (0 where the union is empty).  The outputs of a family that was
+    not given are None.  One launch per family, no synchronisation."""
+    assert (boxes_pred is None) == (boxes_gt is None) and (packed_pred is None) == (packed_gt is None), "det_iou: both sides of a family"
+    assert boxes_pred is not None or packed_pred is not None, "det_iou: boxes, packed masks or both"
+    n = len(pred_idx)
+    assert len(gt_idx) == n
+    dev = boxes_pred.device if boxes_pred is not None else packed_pred[0].device
+    out: Dict[str, Optional[torch.Tensor]] = {"box_iou": None, "inter": None, "union": None, "mask_iou": None}
+    n_pred = n_gt = None
+    wp = ap = wg = ag = None
+    w64 = 0
+    if boxes_pred is not None:
+        assert boxes_pred.dim() == 2 and boxes_pred.shape[1] == 4 and boxes_gt.dim() == 2 and boxes_gt.shape[1] == 4, "boxes: [n, 4] xyxy"
+        assert boxes_pred.is_cuda and boxes_gt.device == dev, "boxes: on one device"
+        boxes_pred, boxes_gt = _f32(boxes_pred, dev), _f32(boxes_gt, dev)
+        n_pred, n_gt = boxes_pred.shape[0], boxes_gt.shape[0]
+        out["box_iou"] = torch.empty((n,), dtype=torch.float32, device=dev)
+    if packed_pred is not None:
+        (wp, ap), (wg, ag) = _packed(packed_pred, "packed_pred"), _packed(packed_gt, "packed_gt")
+        assert wg.device == wp.device == dev and wp.shape[1] == wg.shape[1], "packed masks: one device, one plane size"
+        assert n_pred in (None, wp.shape[0]) and n_gt in (None, wg.shape[0]), "det_iou: boxes and masks describe the same instances"
+        n_pred, n_gt, w64 = wp.shape[0], wg.shape[0], wp.shape[1]
+        out["inter"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        out["union"] = torch.empty((n,), dtype=torch.int32, device=dev)
+        out["mask_iou"] = torch.empty((n,), dtype=torch.float32, device=dev)
+    _det_ids(pred_idx, n_pred, "det_iou: pred_idx")
+    _det_ids(gt_idx, n_gt, "det_iou: gt_idx")
+    if n == 0:
+        return out
+    pred_idx, gt_idx = _i32(pred_idx, dev), _i32(gt_idx, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_det_iou(n, ptr(pred_idx), ptr(gt_idx), n_pred, n_gt, ptr(boxes_pred), ptr(boxes_gt), ptr(wp), ptr(ap), ptr(wg), ptr(ag),
+                               w64, ptr(out["box_iou"]), ptr(out["inter"]), ptr(out["union"]), ptr(out["mask_iou"]), stream_ptr(dev)),
+              "hp_det_iou")
+    return out
+
+
+def coco_thresholds(thresholds) -> np.ndarray:
+    """The float32 thresholds ``hp_det_match`` compares with: ``float32(min(t, 1 - 1e-10))``, pycocotools' cap."""
+    t = np.asarray(thresholds, dtype=np.float64).reshape(-1)
+    return np.ascontiguousarray(np.minimum(t, 1 - 1e-10).astype(np.float32))
+
+
+def det_match(iou: torch.Tensor, n_det, n_gt, gt_ignore, thresholds) -> Dict[str, torch.Tensor]:
+    """``hp_det_match``: COCO's greedy matching of every group at every threshold.  ``iou`` [sum n_det * n_gt] float32 on the
+    device holds the groups' dense detection-major matrices one after the other; ``n_det`` / ``n_gt`` [n_groups] are host
+    columns; ``gt_ignore`` [sum n_gt] bool.  Detections must already be in descending-score order and ground truths with the
+    non-ignored ones first (``evaluation.plan_detection_rows``).  Returns ``det_match`` [n_thr, sum n_det] int32 (ground truth's
+    position in its group or -1), ``det_ignore`` [n_thr, sum n_det] bool and ``gt_match`` [n_thr, sum n_gt] int32."""
+    assert iou.dim() == 1 and iou.dtype == torch.float32 and iou.is_cuda, "iou: [rows] float32 on the device"
+    dev = iou.device
+    n_det, n_gt = np.asarray(n_det, dtype=np.int64).reshape(-1), np.asarray(n_gt, dtype=np.int64).reshape(-1)
+    assert len(n_det) == len(n_gt) and (n_det >= 0).all() and (n_gt >= 0).all(), "det_match: one non-negative n_det and n_gt per group"
+    rows = n_det * n_gt
+    total_rows, total_dets, total_gts = int(rows.sum()), int(n_det.sum()), int(n_gt.sum())
+    assert iou.numel() == total_rows, f"det_match: iou has {iou.numel()} entries, the groups need {total_rows}"
+    assert max(total_rows, total_dets, total_gts) < 2 ** 31, "det_match: tables of 2^31 entries or more"
+    gt_ignore = torch.as_tensor(np.asarray(gt_ignore.cpu() if isinstance(gt_ignore, torch.Tensor) else gt_ignore).astype(np.uint8).reshape(-1))
+    assert gt_ignore.numel() == total_gts, "det_match: one gt_ignore flag per ground truth"
+    thr = coco_thresholds(thresholds)
+    n_thr, n_groups = len(thr), len(n_det)
+    out = {"det_match": torch.empty((n_thr, total_dets), dtype=torch.int32, device=dev),
+           "det_ignore": torch.empty((n_thr, total_dets), dtype=torch.uint8, device=dev),
+           "gt_match": torch.empty((n_thr, total_gts), dtype=torch.int32, device=dev)}
+    if n_groups and n_thr:
+        start = lambda c: np.concatenate([[0], np.cumsum(c)[:-1]])  # noqa: E731
+        tables = [_i32(a, dev) for a in (n_det, n_gt, start(rows), start(n_det), start(n_gt))]
+        gt_ignore, thr_d = gt_ignore.to(dev), torch.as_tensor(thr).to(dev)
+        with torch.cuda.device(dev):
+            check(lib().hp_det_match(n_groups, *[ptr(t) for t in tables], ptr(iou.contiguous()), total_rows, total_dets, total_gts,
+                                     ptr(gt_ignore), ptr(thr_d), n_thr, ptr(out["det_match"]), ptr(out["det_ignore"]), ptr(out["gt_match"]),
+                                     stream_ptr(dev)), "hp_det_match")
+    out["det_ignore"] = out["det_ignore"].view(torch.bool)
+    return out

@@ -845,6 +845,58 @@ int hp_vsd(int n_rows, const int32_t* d_est_layer, const int32_t* d_gt_layer, co
            float delta, int n_tau, const float* taus, int normalized_by_diameter, int32_t* d_counts, int32_t* d_cost,
            float* d_errors, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Scoring 2D detections and instance masks: box IoU, mask IoU and COCO's greedy matching.  The reference has DetectionMeter
+ * (CP/evaluation/meters/detection_meters.py: torchvision's box_iou at one threshold); BOP scores its 2D detection and 2D
+ * segmentation tasks with COCO average precision, which the reference leaves to pycocotools.  The definitions below are the
+ * PUBLISHED ones (torchvision 0.14.1 ops.box_iou; COCOeval.evaluateImg of pycocotools 2.0) restated here in full: neither package
+ * is a dependency, so nothing here could be pinned against them.  csrc/det_eval.hip.
+ *
+ * hp_mask_pack: d_masks [n][h w] uint8 (non-zero = set; the storage of a bool tensor qualifies) -> d_words [n][W64] uint64 and
+ * d_area [n] int32.  W64 = hp_mask_pack_words(h, w) = ceil(h w / 64); bit i of word k is pixel 64 k + i of the flattened plane; the
+ * unused high bits of the last word are 0; d_area[m] is the number of set pixels of mask m.  h w <= 2^24, so that every count is
+ * exact in float32 (hp_mask_pack_words returns -1 outside).  8-byte loads when h w is a multiple of 8 and d_masks is 8-byte aligned
+ * (8 lanes fold their bytes into one word), else byte loads and one wavefront ballot per word.  d_area is zeroed on the stream and
+ * receives one integer atomic per workgroup.
+ *
+ * hp_det_iou: row r compares prediction d_pred_idx[r] with ground truth d_gt_idx[r] (int32 [n_rows], device; 0 <= id < n_pred /
+ * n_gt -- the caller checks them where they still live on the host; a row with an id outside reads nothing and is answered with
+ * NaN IoUs and -1 counts).  Either input family may be NULL, which skips that part and its outputs.
+ *   boxes  d_boxes_pred [n_pred][4], d_boxes_gt [n_gt][4] float32 (x1, y1, x2, y2):
+ *            area = (x2 - x1) (y2 - y1),  wh = max(min(rb) - max(lt), 0),  inter = w h,  iou = inter / (a1 + a2 - inter)
+ *          in float32; 0 / 0 stays NaN.  d_box_iou [n_rows] float32.
+ *   masks  d_words_* / d_area_* as hp_mask_pack writes them, w64 words per mask:
+ *            inter = sum_k popcount(words_pred[k] & words_gt[k]),  union = area_pred + area_gt - inter  (int32: d_inter, d_union)
+ *            d_mask_iou = (float)inter / (float)union, the correctly rounded float32 quotient; 0 where union == 0.
+ * One workgroup per row, integers only: a row's outputs depend on its two masks alone, not on the other rows, their order or the
+ * run.  Rows are in grid x: any n_rows >= 0 works, n_rows == 0 launches nothing.
+ *
+ * hp_det_match: COCO's greedy matching.  Group g (one image and label) owns the dense IoU matrix d_iou[d_row_off[g] + d n_gt[g] + j]
+ * of its n_det[g] detections x n_gt[g] ground truths, detection-major; its outputs start at d_det_off[g] / d_gt_off[g].  All group
+ * tables are int32 [n_groups] on the device, d_gt_ignore is uint8 [total_gts], d_thr float32 [n_thr] (device).  The HOST has ordered
+ * each group: detections by descending score (stable, capped at max_dets), ground truths with the non-ignored ones first (stable).
+ * Rule per threshold, for the detections in order:
+ *   - Among ground truths not yet matched at this threshold, consider the non-ignored ones with iou >= thr and take the largest IoU.
+ *   - Only if there is none, do the same among the ignored ones.
+ *   - An exact tie goes to the ground truth with the higher position.  This is pycocotools' loop with its `<` comparison.
+ *   - The comparison is `>=` in float32 against thr as passed.  The host passes float32(min(t, 1 - 1e-10)).
+ *   - A detection matched to an ignored ground truth is itself ignored.  NaN IoUs never match.
+ * Outputs: d_det_match [n_thr][total_dets] int32 = the ground truth's position in its group or -1; d_det_ignore [n_thr][total_dets]
+ * uint8; d_gt_match [n_thr][total_gts] int32 = the detection's position in its group or -1.  One wavefront per (group, threshold),
+ * lanes strided over the ground truths (any n_gt), detections sequential.  Groups with n_det == 0 or n_gt == 0 are legal.  A group
+ * whose ranges leave the tables (total_rows, total_dets, total_gts) touches nothing.
+ * ---------------------------------------------------------------------------------- */
+int64_t hp_mask_pack_words(int h, int w);
+int hp_mask_pack(int n, int h, int w, const uint8_t* d_masks, uint64_t* d_words, int32_t* d_area, void* stream);
+int hp_det_iou(int n_rows, const int32_t* d_pred_idx, const int32_t* d_gt_idx, int n_pred, int n_gt, const float* d_boxes_pred,
+               const float* d_boxes_gt, const uint64_t* d_words_pred, const int32_t* d_area_pred, const uint64_t* d_words_gt,
+               const int32_t* d_area_gt, int w64, float* d_box_iou, int32_t* d_inter, int32_t* d_union, float* d_mask_iou,
+               void* stream);
+int hp_det_match(int n_groups, const int32_t* d_n_det, const int32_t* d_n_gt, const int32_t* d_row_off, const int32_t* d_det_off,
+                 const int32_t* d_gt_off, const float* d_iou, int64_t total_rows, int64_t total_dets, int64_t total_gts,
+                 const uint8_t* d_gt_ignore, const float* d_thr, int n_thr, int32_t* d_det_match, uint8_t* d_det_ignore,
+                 int32_t* d_gt_match, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -124,23 +124,43 @@ def default_coarse_precision(model_name: str) -> str:
     return "f16" if NAMED_MODELS[model_name]["inference_parameters"]["n_pose_hypotheses"] > 1 else "f32"
 
 
+def make_depth_refiner(name: Optional[str], mesh_db, renderer):
+    """The depth refiner a model entry (or ``InferenceConfig.depth_refiner``) names: ``"icp"`` -> :class:`ICPRefiner`,
+    ``"teaserpp"`` -> :class:`TeaserppRefiner` (``MP/evaluation/evaluation.py:170-180``), in any letter case; ``None`` -> none."""
+    if name is None:
+        return None
+    kind = str(name).lower()
+    if kind == "icp":
+        from .icp_refiner import ICPRefiner
+
+        return ICPRefiner(mesh_db, renderer)
+    if kind == "teaserpp":
+        from .teaserpp_refiner import TeaserppRefiner
+
+        return TeaserppRefiner(mesh_db, renderer)
+    raise ValueError(f"unknown depth refiner {name!r} (icp, teaserpp)")
+
+
+_ENTRY = "entry"  # load_named_model(depth_refiner=...): keep what the model entry names
+
+
 def load_named_model(model_name: str, object_dataset: RigidObjectDataset, n_workers: int = 4, bsz_images: int = 128,
-                     models_root: Optional[Path] = None, device="cuda", coarse_precision: Optional[str] = None) -> PoseEstimator:
+                     models_root: Optional[Path] = None, device="cuda", coarse_precision: Optional[str] = None,
+                     depth_refiner: Optional[str] = _ENTRY) -> PoseEstimator:
     """``TB/utils/load_model.py:52-88``.  ``coarse_precision`` (beyond the reference's signature): ``"f16"`` plans the coarse /
     scoring network in fp16, ``"f32"`` in the reference's arithmetic; ``None`` = :func:`default_coarse_precision` (fp16 for the
     multi-hypothesis configurations).  The refiner always runs in fp32.  Measured on the end-to-end frame: ``bench.py`` keys
-    ``e2e`` / ``e2e_f16_coarse``, each with its parity against the oracle estimator."""
+    ``e2e`` / ``e2e_f16_coarse``, each with its parity against the oracle estimator.  ``depth_refiner`` (also beyond the
+    reference's signature) overrides the entry's depth refiner with ``None``, ``"icp"`` or ``"teaserpp"``; left out, the
+    entry decides."""
     model = NAMED_MODELS[model_name]
     if coarse_precision is None:
         coarse_precision = default_coarse_precision(model_name)
+    refiner_name = model.get("depth_refiner") if depth_refiner == _ENTRY else depth_refiner
     coarse_model, refiner_model, mesh_db = load_pose_models(
         coarse_run_id=model["coarse_run_id"], refiner_run_id=model["refiner_run_id"], object_dataset=object_dataset,
         force_panda3d_renderer=True, renderer_kwargs={"preload_cache": False, "split_objects": False, "n_workers": n_workers},
         models_root=models_root, device=device, max_batch=bsz_images, coarse_precision=coarse_precision)
-    depth_refiner = None
-    if model.get("depth_refiner") == "ICP":
-        from .icp_refiner import ICPRefiner
-
-        depth_refiner = ICPRefiner(mesh_db, refiner_model.renderer)
     return PoseEstimator(refiner_model=refiner_model, coarse_model=coarse_model, detector_model=None,
-                         depth_refiner=depth_refiner, bsz_objects=8, bsz_images=bsz_images)
+                         depth_refiner=make_depth_refiner(refiner_name, mesh_db, refiner_model.renderer), bsz_objects=8,
+                         bsz_images=bsz_images)

@@ -568,6 +568,40 @@ int hp_icp_refine(int n, int B, int H, int W, const float* d_depth_rendered, con
                   void* stream);
 
 /* ------------------------------------------------------------------------------------
+ * Depth refinement, second kind (depth_refiner = "teaserpp"): robust registration between the depth rendered at the
+ * predicted pose and the measured depth.  Replaces compute_teaserpp_refinement / TeaserppRefiner.refine_poses
+ * (MP/inference/teaserpp_refiner.py:54-294); the solver is the teaserpp_python library there and a restatement of its
+ * published definition here, with a deterministic GREEDY clique in place of the exact maximum clique (parity unpinned, see
+ * csrc/teaser.hip for the definition).  Results are bit-identical from run to run.
+ *  hp_teaser_fps: farthest-point sampling of n point sets, d_points [n][n_max][3], d_counts [n] points each: starts at
+ *    index 0, takes the point farthest from the chosen set, ties to the lowest index.  d_indices [n][k]: min(k, count)
+ *    indices in selection order, then -1.  d_scratch [n][n_max] floats.
+ *  hp_teaser_register: b ~ R a + t for n sets of d_m[i] <= m_max <= 1024 correspondences, d_a / d_b [n][m_max][3].  d_T [n][16]
+ *    (identity when rejected), d_status [n]: 0 accepted, -1 d_m[i] negative (the refinement's "too few masked pixels"),
+ *    -2 clique smaller than 3, -3 fewer than min_num_inliers inliers (|R a + t - b| < noise_bound over the d_m[i]
+ *    correspondences).  d_num_inliers [n], d_clique_size [n], d_clique_mask [n][32] (bit j of word w: correspondence
+ *    32 w + j) may be NULL.
+ *  hp_teaser_refine: the whole refinement, shaped like hp_icp_refine: mask (rendered > 0 & measured > 0, with
+ *    use_threshold_mask also |measured - rendered| <= depth_delta_thresh), fewer than n_min_points pixels -> -1;
+ *    back-projection x = (u - cx) d / fx, y = (v - cy) d / fy, z = d; min(n_points, N) correspondences by farthest-point
+ *    sampling of the rendered points (use_farthest_point_sampling = 0: the evenly spaced indices floor(k N / M));
+ *    registration; d_TCO_out = T d_TCO where accepted, d_TCO bit for bit otherwise.  d_num_inliers / d_clique_size may be
+ *    NULL.  d_workspace: hp_teaser_workspace_bytes(n, H, W, n_points) bytes (-1 for sizes out of range: n_points 1 .. 1024).
+ * ---------------------------------------------------------------------------------- */
+int64_t hp_teaser_workspace_bytes(int n, int H, int W, int n_points);
+int hp_teaser_fps(int n, int n_max, const float* d_points, const int32_t* d_counts, int k, float* d_scratch,
+                  int32_t* d_indices, void* stream);
+int hp_teaser_register(int n, int m_max, const float* d_a, const float* d_b, const int32_t* d_m, double noise_bound,
+                       int min_num_inliers, float* d_T, int32_t* d_status, int32_t* d_num_inliers, int32_t* d_clique_size,
+                       uint32_t* d_clique_mask, void* stream);
+int hp_teaser_refine(int n, int B, int H, int W, const float* d_depth_rendered, const float* d_depth_measured,
+                     const int32_t* d_im_ids, const int32_t* h_im_ids, const float* d_K, const float* d_TCO,
+                     int use_threshold_mask, float depth_delta_thresh, int n_min_points, int n_points,
+                     int use_farthest_point_sampling, double noise_bound, int min_num_inliers, float* d_TCO_out,
+                     int32_t* d_retval, int32_t* d_num_inliers, int32_t* d_clique_size, void* d_workspace,
+                     int64_t workspace_bytes, void* stream);
+
+/* ------------------------------------------------------------------------------------
  * Detector stages that are not convolutions (the reference's Detector.get_detections, MP/inference/detector.py:34-156, runs
  * torchvision's MaskRCNN.forward; file references below are torchvision 0.14.1, pinned by the reference's pyproject.toml).
  * The dense networks are hp_net objects: HP_ARCH_RESNET50_FPN (backbone + FPN + RPN head) and two HP_ARCH_CUSTOM graphs

@@ -136,6 +136,9 @@ _PROTOS = {
     "hp_icp_refine": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_void_p, C.c_void_p, C.c_void_p,
                                 c_f32p, c_f32p, C.c_int, C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p, c_f32p,
                                 C.c_void_p]),
+    "hp_icp_target_table": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, C.c_void_p]),
+    "hp_icp_accumulate": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_u8p, c_i32p, c_f32p, c_f32p, c_f32p,
+                                    C.c_int, C.c_float, C.c_float, c_f32p, C.c_void_p]),
     "hp_teaser_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
     "hp_teaser_fps": (C.c_int, [C.c_int, C.c_int, c_f32p, c_i32p, C.c_int, c_f32p, c_i32p, C.c_void_p]),
     "hp_teaser_register": (C.c_int, [C.c_int, C.c_int, c_f32p, c_f32p, c_i32p, C.c_double, C.c_int, c_f32p, c_i32p, c_i32p, c_i32p,

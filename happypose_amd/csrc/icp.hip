@@ -21,9 +21,20 @@
 //     residual r = n.(q - p'), Jacobian [p' x n, n]; the 6x6 normal equations are accumulated in
 //     two deterministic stages (per-block partial sums, then a fixed-order sum in fp64), solved by
 //     Cholesky and the increment composed as a rotation vector;
-//   * residual reported = RMS of r over the inliers of the last iteration.
-// oracle/icp.py restates exactly this definition on the CPU; tests compare against it and check
-// that known perturbations of a synthetic scene are recovered.
+//   * residual reported = RMS of r over the inliers of the final increment for an accepted
+//     prediction, -1 for a rejected one (its pose is the input pose bit for bit).  A prediction
+//     is rejected when its start set has fewer than n_min_points pixels, when an iteration finds
+//     fewer than 6 correspondences or its Cholesky factorisation fails, or when the final
+//     increment has fewer than n_min_points inliers.  |r| = |n.(q - p')| <= |q - p'| <= tol for
+//     every inlier (n is a unit vector), so the RMS cannot exceed the tolerance: the test
+//     "residual > tolerance" of the reference is kept in the finalize kernel but nothing reaches
+//     it, and every accepted prediction has residual <= tolerance.
+//   * the diagonal of the normal equations gets 1e-9 trace + 1e-12 before the factorisation: a
+//     surface that leaves directions unconstrained (one fronto-parallel plane: rotation about z
+//     and translation in x, y) is still solved, with a zero increment in those directions.
+// oracle/icp.py restates exactly this definition on the CPU in rounded fp32, tests/icp_ref.py in
+// float64.  The stages are reachable on their own for the tests: hp_icp_target_table and
+// hp_icp_accumulate launch the kernels of hp_icp_refine through the same two functions below.
 #include <cmath>
 #include <vector>
 
@@ -42,7 +53,7 @@ struct IcpArgs {
   const int32_t* im_ids;  // [n]
   const float* K;         // [n][9]
   const float* tgt;       // [B][H][W][6]  point + normal of the measured depth (point.z = 0: invalid)
-  float* T;               // [n][12]       current increment, rows of [R | t]
+  const float* T;         // [n][12]       current increment, rows of [R | t]
   float* partial;         // [n][kBlocksPerView][kAccum]
   int n, H, W;
   float tol, delta_thresh;
@@ -258,10 +269,15 @@ __global__ void icp_finalize_kernel(const float* T, const float* stats, const fl
       O[i * 4 + j] = v;
     }
   if (retval) retval[n] = ok ? 0 : -1;
-  if (residual) residual[n] = st[2];
+  if (residual) residual[n] = ok ? st[2] : -1.f;
 }
 
 struct IcpWorkspace { float* tgt = nullptr; size_t tgt_bytes = 0; float* small = nullptr; size_t small_bytes = 0; int32_t* first = nullptr; size_t first_bytes = 0; };
+
+IcpWorkspace& workspace() {
+  static IcpWorkspace ws;  // grown on demand; calls are expected on one stream per process
+  return ws;
+}
 
 template <typename T>
 int grow(T** p, size_t* have, size_t need) {
@@ -273,10 +289,53 @@ int grow(T** p, size_t* have, size_t need) {
   return HP_OK;
 }
 
+// h_first [B]: the prediction whose row of K holds the intrinsics of image b (-1: none, the image's table is zero)
+int launch_target(int B, int H, int W, const float* d_depth_measured, const float* d_K, const int32_t* h_first, float* d_tgt,
+                  hipStream_t st) {
+  IcpWorkspace& ws = workspace();
+  int rc;
+  if ((rc = grow(&ws.first, &ws.first_bytes, (size_t)B * sizeof(int32_t)))) return rc;
+  HP_CHECK_HIP(hipMemcpyAsync(ws.first, h_first, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HP_CHECK_HIP(hipStreamSynchronize(st));  // `h_first` is a stack-lifetime host buffer
+  const int64_t total = (int64_t)B * H * W;
+  hipLaunchKernelGGL(icp_target_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_depth_measured, d_K, ws.first,
+                     d_tgt, B, H, W);
+  return check_launch("icp_target_kernel");
+}
+
+int launch_accumulate(const IcpArgs& a, hipStream_t st) {
+  hipLaunchKernelGGL(icp_accumulate_kernel, dim3(kBlocksPerView, a.n), dim3(256), 0, st, a);
+  return check_launch("icp_accumulate_kernel");
+}
+
 }  // namespace
 }  // namespace hp
 
 using namespace hp;
+
+extern "C" int hp_icp_target_table(int B, int H, int W, const float* d_depth_measured, const float* d_K, float* d_tgt_out,
+                                   void* stream) {
+  HP_REQUIRE(B >= 1 && H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX, "hp_icp_target_table: bad sizes");
+  HP_REQUIRE(d_depth_measured && d_K && d_tgt_out, "hp_icp_target_table: null pointer");
+  std::vector<int32_t> first(B);
+  for (int b = 0; b < B; ++b) first[b] = b;  // one row of K per image
+  return launch_target(B, H, W, d_depth_measured, d_K, first.data(), d_tgt_out, (hipStream_t)stream);
+}
+
+extern "C" int hp_icp_accumulate(int n, int B, int H, int W, const float* d_depth_rendered, const float* d_depth_measured,
+                                 const uint8_t* d_masks, const int32_t* d_im_ids, const float* d_K, const float* d_tgt,
+                                 const float* d_T, int mode, float tolerance, float depth_delta_thresh, float* d_partial_out,
+                                 void* stream) {
+  HP_REQUIRE(n >= 1 && B >= 1 && H > 0 && W > 0 && (int64_t)H * W <= INT32_MAX, "hp_icp_accumulate: bad sizes");
+  HP_REQUIRE(mode == 0 || mode == 1, "hp_icp_accumulate: mode is 0 (centroids) or 1 (normal equations)");
+  HP_REQUIRE(d_depth_rendered && d_depth_measured && d_im_ids && d_K && d_tgt && d_T && d_partial_out,
+             "hp_icp_accumulate: null pointer");
+  IcpArgs a{};
+  a.depth_r = d_depth_rendered; a.depth_m = d_depth_measured; a.masks = d_masks; a.im_ids = d_im_ids; a.K = d_K;
+  a.tgt = d_tgt; a.T = d_T; a.partial = d_partial_out; a.n = n; a.H = H; a.W = W; a.tol = tolerance; a.delta_thresh = depth_delta_thresh;
+  a.mode = mode;
+  return launch_accumulate(a, (hipStream_t)stream);
+}
 
 extern "C" int hp_icp_refine(int n, int B, int H, int W, const float* d_depth_rendered, const float* d_depth_measured,
                              const uint8_t* d_masks, const int32_t* d_im_ids, const int32_t* h_im_ids, const float* d_K,
@@ -287,43 +346,35 @@ extern "C" int hp_icp_refine(int n, int B, int H, int W, const float* d_depth_re
   if (n == 0) return HP_OK;
   HP_REQUIRE(d_depth_rendered && d_depth_measured && d_im_ids && h_im_ids && d_K && d_TCO && d_TCO_out,
              "hp_icp_refine: null pointer");
-  static IcpWorkspace ws;  // grown on demand; calls are expected on one stream per process
+  IcpWorkspace& ws = workspace();
   hipStream_t st = (hipStream_t)stream;
   int rc;
   const size_t HW = (size_t)H * W;
   if ((rc = grow(&ws.tgt, &ws.tgt_bytes, (size_t)B * HW * 6 * sizeof(float)))) return rc;
   const size_t small_floats = (size_t)n * (12 + 4 + (size_t)kBlocksPerView * kAccum);
   if ((rc = grow(&ws.small, &ws.small_bytes, small_floats * sizeof(float)))) return rc;
-  if ((rc = grow(&ws.first, &ws.first_bytes, (size_t)B * sizeof(int32_t)))) return rc;
   // the intrinsics of an image are those of its first prediction (K is indexed per prediction)
   std::vector<int32_t> first(B, -1);
   for (int i = n - 1; i >= 0; --i) {
     HP_REQUIRE(h_im_ids[i] >= 0 && h_im_ids[i] < B, "hp_icp_refine: batch_im_id out of range");
     first[h_im_ids[i]] = i;
   }
-  HP_CHECK_HIP(hipMemcpyAsync(ws.first, first.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
-  HP_CHECK_HIP(hipStreamSynchronize(st));  // `first` is a stack-lifetime host buffer
   float* T = ws.small;
   float* stats = T + (size_t)n * 12;
   float* partial = stats + (size_t)n * 4;
-  const int64_t total = (int64_t)B * HW;
-  hipLaunchKernelGGL(icp_target_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, d_depth_measured, d_K, ws.first,
-                     ws.tgt, B, H, W);
-  if ((rc = check_launch("icp_target_kernel"))) return rc;
+  if ((rc = launch_target(B, H, W, d_depth_measured, d_K, first.data(), ws.tgt, st))) return rc;
   IcpArgs a{};
   a.depth_r = d_depth_rendered; a.depth_m = d_depth_measured; a.masks = d_masks; a.im_ids = d_im_ids; a.K = d_K;
   a.tgt = ws.tgt; a.T = T; a.partial = partial; a.n = n; a.H = H; a.W = W; a.tol = tolerance; a.delta_thresh = depth_delta_thresh;
   for (int it = 0; it <= n_iterations; ++it) {
     a.mode = it == 0 ? 0 : 1;  // pass 0: centroid start; the final pass only evaluates the residual
-    hipLaunchKernelGGL(icp_accumulate_kernel, dim3(kBlocksPerView, n), dim3(256), 0, st, a);
-    if ((rc = check_launch("icp_accumulate_kernel"))) return rc;
+    if ((rc = launch_accumulate(a, st))) return rc;
     hipLaunchKernelGGL(icp_update_kernel, dim3((n + 63) / 64), dim3(64), 0, st, partial, T, stats, n, a.mode, n_min_points);
     if ((rc = check_launch("icp_update_kernel"))) return rc;
   }
   // residual of the final increment
   a.mode = 1;
-  hipLaunchKernelGGL(icp_accumulate_kernel, dim3(kBlocksPerView, n), dim3(256), 0, st, a);
-  if ((rc = check_launch("icp_accumulate_kernel"))) return rc;
+  if ((rc = launch_accumulate(a, st))) return rc;
   hipLaunchKernelGGL(icp_update_kernel, dim3((n + 63) / 64), dim3(64), 0, st, partial, T, stats, n, 2, n_min_points);
   if ((rc = check_launch("icp_update_kernel"))) return rc;
   hipLaunchKernelGGL(icp_finalize_kernel, dim3((n + 63) / 64), dim3(64), 0, st, T, stats, d_TCO, d_TCO_out, d_retval, d_residual, n,

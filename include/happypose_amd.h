@@ -559,13 +559,30 @@ int hp_probe_mfma_rate(int random_data, double* tflops, double* shader_mhz, void
  * d_depth_measured [B][H][W] metres, d_masks [B][H][W] u8 or NULL (= the "threshold" mask with
  * depth_delta_thresh), im_ids on device and host, d_K [n][9].  Outputs: d_TCO_out [n][16]
  * (= input pose where the registration is rejected), d_retval [n] (0 / -1), d_residual [n]
- * (RMS point-to-plane distance of the inliers, metres); the last two may be NULL.
+ * (RMS point-to-plane distance of the inliers, metres, <= tolerance; -1 where rejected); the last
+ * two may be NULL.
+ * The two stages of an iteration on their own, through the launches hp_icp_refine makes:
+ *  hp_icp_target_table: points and unit normals of d_depth_measured [B][H][W] with ONE row of
+ *    d_K [B][9] per image -> d_tgt_out [B][H][W][6] (zeros where the depth is not > 0).
+ *  hp_icp_accumulate: one pass over the pixels of n predictions with the caller's table d_tgt
+ *    [B][H][W][6] and increments d_T [n][12] (rows of [R | t]; not read in mode 0) ->
+ *    d_partial_out [n][64][32], the per-block sums whose fixed-order fp64 sum hp_icp_refine solves.
+ *    mode 0: sums of the source points [0..2] and of the measured points at the same pixels
+ *    [3..5], count [27].  mode 1: upper triangle of J^T J row by row [0..20], J^T r [21..26],
+ *    count [27], sum r^2 [28].  Other entries are 0.  d_im_ids [n] must lie in 0 .. B-1 (on the
+ *    device: not checked).
  * ---------------------------------------------------------------------------------- */
 int hp_icp_refine(int n, int B, int H, int W, const float* d_depth_rendered, const float* d_depth_measured,
                   const uint8_t* d_masks, const int32_t* d_im_ids, const int32_t* h_im_ids, const float* d_K,
                   const float* d_TCO, int n_iterations, int n_min_points, float tolerance,
                   float depth_delta_thresh, float* d_TCO_out, int32_t* d_retval, float* d_residual,
                   void* stream);
+int hp_icp_target_table(int B, int H, int W, const float* d_depth_measured, const float* d_K, float* d_tgt_out,
+                        void* stream);
+int hp_icp_accumulate(int n, int B, int H, int W, const float* d_depth_rendered, const float* d_depth_measured,
+                      const uint8_t* d_masks, const int32_t* d_im_ids, const float* d_K, const float* d_tgt,
+                      const float* d_T, int mode, float tolerance, float depth_delta_thresh, float* d_partial_out,
+                      void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Depth refinement, second kind (depth_refiner = "teaserpp"): robust registration between the depth rendered at the

@@ -64,7 +64,8 @@ def target_table(depth, K):
 
 def icp_refine(depth_rendered, depth_measured, K, TCO, mask=None, n_iterations=30, n_min_points=1000, tolerance=0.05,
                depth_delta_thresh=0.1):
-    """One prediction.  Returns ``(TCO_refined [4,4], retval, residual)``."""
+    """One prediction.  Returns ``(TCO_refined [4,4], retval, residual)``; a rejected prediction keeps its pose and reports
+    the residual -1, whatever the reason (the definition in ``icp.hip``)."""
     dr, dm = depth_rendered.astype(np.float32), depth_measured.astype(np.float32)
     H, W = dr.shape
     if mask is None:
@@ -119,7 +120,7 @@ def icp_refine(depth_rendered, depth_measured, K, TCO, mask=None, n_iterations=3
         return TCO.copy(), -1, -1.0
     residual = float(np.sqrt(((nq * (q - p)).sum(-1) ** 2).mean()))
     if residual > tolerance or len(p) < n_min_points:
-        return TCO.copy(), -1, residual
+        return TCO.copy(), -1, -1.0
     T = np.eye(4)
     T[:3, :3], T[:3, 3] = R, t
     return (T @ TCO.astype(np.float64)).astype(np.float32), 0, residual

@@ -184,6 +184,9 @@ _PROTOS = {
                              c_f32p, c_i32p, c_i32p, c_f32p, C.c_void_p]),
     "hp_det_match": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, c_i32p, c_f32p, C.c_int64, C.c_int64, C.c_int64, c_u8p, c_f32p,
                                C.c_int, c_i32p, c_u8p, c_i32p, C.c_void_p]),
+    "hp_mesh_sample_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
+    "hp_mesh_sample_surface": (C.c_int, [C.c_int, c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_uint64, c_f32p, c_i32p, C.c_void_p,
+                                         C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

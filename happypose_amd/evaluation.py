@@ -459,6 +459,101 @@ class PoseErrorMeter:
         return summary, {"gt": gt_df, "matches": matches_df, "preds": pred_df, "ap": ap_dfs}
 
 
+# ---- the ModelNet meter (MP/evaluation/meters/modelnet_meters.py) ------------------------------------------------------------------
+def one_to_one_matching(pred_infos: pd.DataFrame, gt_infos: pd.DataFrame, keys=("scene_id", "view_id"),
+                        allow_pred_missing: bool = False) -> pd.DataFrame:
+    """``MP/evaluation/meters/utils.py:23-41``: predictions joined to ground truths on ``keys``; a key met by more than one pair,
+    or (unless ``allow_pred_missing``) a ground truth without exactly one prediction, is an ``AssertionError``."""
+    keys = list(keys)
+    pred_infos["pred_id"] = np.arange(len(pred_infos))
+    gt_infos["gt_id"] = np.arange(len(gt_infos))
+    matches = pred_infos.merge(gt_infos, on=keys, suffixes=("", "_gt"))
+    assert not matches.duplicated(keys).any(), "one_to_one_matching: more than one (prediction, ground truth) pair for a key"
+    if not allow_pred_missing:
+        assert len(matches) == len(gt_infos), "one_to_one_matching: a ground truth without a prediction"
+    return matches
+
+
+def angular_distance_deg(R_gt: np.ndarray, R_pred: np.ndarray, eps: float = 1e-7) -> np.ndarray:
+    """``angular_distance`` of the unit quaternions of two rotations (``MP/evaluation/meters/lf_utils.py:30-40``), in degrees:
+    ``2 acos(min(|q_gt . q_pred|, 1 - eps))`` with ``|q_gt . q_pred| = sqrt(max(trace(R_gt^T R_pred) + 1, 0)) / 2``, in float64
+    on the host.  ``[n, 3, 3]`` each."""
+    R_gt, R_pred = np.asarray(R_gt, np.float64).reshape(-1, 3, 3), np.asarray(R_pred, np.float64).reshape(-1, 3, 3)
+    trace = np.einsum("nij,nij->n", R_gt, R_pred)
+    dot = np.sqrt(np.maximum(trace + 1.0, 0.0)) / 2.0
+    return np.rad2deg(2.0 * np.arccos(np.minimum(dot, 1.0 - eps)))
+
+
+class ModelNetErrorMeter:
+    """The reference's ModelNet meter: ``add0.1d``, ``5deg_5cm`` and ``proj2d_5px`` over one-to-one matched frames.
+
+    ``mesh_db``: a ``MeshDataBase``, batched here with ``resample_n_points=sample_n_points`` (points drawn uniformly from each
+    surface on the device), or tables that are already batched.  The reference scores one match per :meth:`add`; here every
+    match of a call goes through ONE ``hp_pose_errors`` launch: an ADD row (``norm_avg`` = ``add``, ``TCO_norm`` = ``trans_dist``)
+    and an MSPD row against an identity-only symmetry table (``norm_avg`` = the mean reprojection distance under ``gt.K``) per
+    match.  ``summary()`` returns pandas, not xarray, like the other meters."""
+
+    def __init__(self, mesh_db, sample_n_points=None, device="cuda"):
+        batched = mesh_db.batched(resample_n_points=sample_n_points) if hasattr(mesh_db, "batched") else mesh_db
+        # the norm of the extent of each object's own points, in float32 like the reference's tensors
+        pts = np.asarray(batched.points.cpu() if isinstance(batched.points, torch.Tensor) else batched.points, dtype=np.float32)
+        self.diameters = {}
+        for o, label in enumerate(batched.labels):
+            own = pts[o, :batched.infos[label]["n_points"]]
+            self.diameters[label] = float(np.linalg.norm(own.max(0) - own.min(0)))
+        self.mesh_db = batched.to(device).float()
+        self.device = device
+        self.reset()
+
+    def reset(self):
+        self.datas = defaultdict(list)
+
+    def is_data_valid(self, data) -> bool:
+        return hasattr(data, "K")
+
+    def compute_errors(self, TXO_pred: torch.Tensor, TXO_gt: torch.Tensor, labels, K: torch.Tensor) -> Dict[str, np.ndarray]:
+        """``add``, ``proj_error`` and ``trans_dist`` ``[n]`` of ``n`` (prediction, ground truth) pairs: one launch of ``2 n`` rows."""
+        n = len(labels)
+        if n == 0:
+            return {k: np.zeros(0) for k in ("add", "proj_error", "trans_dist")}
+        t = self.mesh_db.device_tables
+        dev = t["points"].device
+        n_obj = t["points"].shape[0]
+        ids = np.tile(np.arange(n, dtype=np.int32), 2)
+        obj_ids = np.tile(self.mesh_db.ids_of(labels), 2)
+        modes = np.repeat(np.asarray([ops.POSE_ERR_MODES["ADD"], ops.POSE_ERR_MODES["MSPD"]], np.int32), n)
+        identity = torch.eye(4, dtype=torch.float32, device=dev).expand(n_obj, 1, 4, 4).contiguous()
+        n_pts = torch.as_tensor(np.asarray([self.mesh_db.infos[label]["n_points"] for label in self.mesh_db.labels], np.int32)).to(dev)
+        K2 = torch.cat([K, K]).to(dev)
+        out = ops.pose_errors_tables(ids, ids, obj_ids, modes, TXO_pred, TXO_gt, t["points"], identity,
+                                     torch.ones(n_obj, dtype=torch.int32, device=dev), n_pts, K=K2)
+        norm_avg, tco_norm = out["norm_avg"].cpu().numpy().astype(np.float64), out["TCO_norm"].cpu().numpy().astype(np.float64)
+        return {"add": norm_avg[:n], "proj_error": norm_avg[n:], "trans_dist": tco_norm[:n]}
+
+    def add(self, pred_data, gt_data):
+        pred_data, gt_data = pred_data.float(), gt_data.float()
+        matches = one_to_one_matching(pred_data.infos, gt_data.infos, keys=("scene_id", "view_id"), allow_pred_missing=False)
+        pred_ids, gt_ids = matches["pred_id"].to_numpy(), matches["gt_id"].to_numpy()
+        labels = matches["label"].to_numpy()  # the prediction's label, as in the reference
+        TXO_pred, TXO_gt = pred_data.poses[pred_ids], gt_data.poses[gt_ids]
+        errors = self.compute_errors(TXO_pred, TXO_gt, labels, gt_data.K[gt_ids])
+        df = matches.reset_index(drop=True)
+        df["add"] = errors["add"]
+        df["diameter"] = np.asarray([self.diameters[label] for label in labels], dtype=np.float64)
+        df["proj_error"] = errors["proj_error"]
+        df["angular_dist"] = angular_distance_deg(TXO_gt[:, :3, :3].cpu().numpy(), TXO_pred[:, :3, :3].cpu().numpy())
+        df["trans_dist"] = errors["trans_dist"]
+        self.datas["df"].append(df)
+
+    def summary(self):
+        df = pd.concat(self.datas["df"], ignore_index=True)
+        df.index.name = "match_id"
+        add = df["add"].to_numpy() < 0.1 * df["diameter"].to_numpy()
+        rot_trans = np.logical_and(df["trans_dist"].to_numpy() < 0.05, df["angular_dist"].to_numpy() < 5)
+        proj_2d = df["proj_error"].to_numpy() < 5
+        return {"add0.1d": add.mean(), "5deg_5cm": rot_trans.mean(), "proj2d_5px": proj_2d.mean()}, df
+
+
 # ---- visible-surface discrepancy (BOP's third pose error) ------------------------------------------------------------------------
 BOP_VSD_DELTA = 0.015                                                 # metres
 BOP_VSD_TAUS = tuple(round(0.05 * k, 2) for k in range(1, 11))        # 0.05 ... 0.50, fractions of the diameter

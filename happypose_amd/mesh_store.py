@@ -216,14 +216,21 @@ class MeshDataBase:
     def from_object_ds(object_ds: RigidObjectDataset) -> "MeshDataBase":
         return MeshDataBase([object_ds[n] for n in range(len(object_ds))])
 
-    def batched(self, aabb: bool = False, resample_n_points: Optional[int] = None, n_sym: int = 64) -> BatchedMeshes:
+    def batched(self, aabb: bool = False, resample_n_points: Optional[int] = None, n_sym: int = 64, resample_seed: int = 0,
+                resample_method: str = "random", resample_oversample: int = 8) -> BatchedMeshes:
         """``CP/lib3d/rigid_mesh_database.py:27-78``.  ``aabb=True``: the points are the 8 corners of the bounding
         box; ``n_sym``: rotations per continuous symmetry axis.  The no-argument call gives the same points as
-        before; the symmetry table is always attached."""
+        before; the symmetry table is always attached.
+
+        ``resample_n_points=N``: every object's table is ``N`` points.  A mesh with faces is resampled on the device
+        (:meth:`resample_surface`); a mesh without faces (a point cloud) takes the reference's other branch
+        (``TB/lib3d/rigid_mesh_database.py:96-101``), the deterministic vertex subset :func:`sample_point_ids`, on the host."""
         if aabb:
             assert resample_n_points is None
+        resampled = {}
         if resample_n_points:
-            raise NotImplementedError("resample_n_points needs trimesh's surface sampling, which is not a dependency")
+            resampled = self.resample_surface(int(resample_n_points), seed=resample_seed, method=resample_method,
+                                              oversample=resample_oversample)
         labels, points, symmetries, unsupported = [], [], [], []
         new_infos = deepcopy(self.infos)
         for label, mesh in self.meshes.items():
@@ -231,6 +238,8 @@ class MeshDataBase:
             pts = np.asarray(mesh.vertices, dtype=np.float64)
             if aabb:
                 pts = bounding_box_corners(pts)
+            elif resample_n_points:
+                pts = resampled[label] if label in resampled else pts[sample_point_ids(len(pts), int(resample_n_points))]
             pts = pts * obj.scale
             try:
                 sym = make_bop_symmetries(obj.symmetries_discrete, obj.symmetries_continuous, n_sym,
@@ -250,6 +259,41 @@ class MeshDataBase:
         for n, s in enumerate(symmetries):
             sym[n, :len(s)] = s
         return BatchedMeshes(new_infos, np.array(labels), pts, sym.astype(np.float32), unsupported_symmetries=unsupported)
+
+    def resample_surface(self, n_points: int, seed: int = 0, method: str = "random", oversample: int = 8, device="cuda") -> Dict[str, np.ndarray]:
+        """``n_points`` points on the surface of every mesh that has faces: ``{label: [n_points, 3] float64}`` in MESH units,
+        drawn on the device by ``ops.mesh_sample_surface`` (area-uniform; the definition is in ``include/happypose_amd.h``).
+        Object ``o`` of the random stream is the object's position in ``self.meshes``, so a label's points do not depend on
+        which other meshes have faces.  ``method="fps"`` draws ``oversample * n_points`` samples and keeps ``n_points`` of them
+        by farthest-point sampling (``ops.farthest_point_ids``; the first sample starts the selection), in selection order."""
+        assert method in ("random", "fps"), f"resample_method {method!r}: 'random' or 'fps'"
+        assert n_points >= 1 and (method == "random" or oversample >= 1)
+        labels = list(self.meshes)
+        with_faces = [label for label in labels if len(self.meshes[label].faces)]
+        if not with_faces:
+            return {}
+        import torch
+
+        if not torch.cuda.is_available():  # there is no CPU implementation of the surface draw, and none is substituted
+            raise NotImplementedError("resample_n_points on a mesh with faces is drawn on the device (hp_mesh_sample_surface): "
+                                      "no GPU is available and there is no CPU implementation")
+        from . import ops  # the device library is needed from here on (ops imports this module)
+
+        # every mesh keeps its position; one without faces is passed empty and its (NaN) rows are not read
+        verts = [self.meshes[label].vertices if label in with_faces else np.zeros((0, 3)) for label in labels]
+        faces = [self.meshes[label].faces if label in with_faces else np.zeros((0, 3), np.int32) for label in labels]
+        n_draw = n_points * oversample if method == "fps" else n_points
+        pts = ops.mesh_sample_surface(verts, faces, n_draw, seed=seed, device=device)
+        if method == "fps":
+            counts = torch.as_tensor([n_draw if label in with_faces else 0 for label in labels], dtype=torch.int32)
+            ids = ops.farthest_point_ids(pts, counts, n_points).long().clamp_(min=0)
+            pts = torch.gather(pts, 1, ids.unsqueeze(-1).expand(-1, -1, 3))
+        pts = pts.cpu().numpy().astype(np.float64)
+        out = {label: pts[o] for o, label in enumerate(labels) if label in with_faces}
+        no_area = [label for label, p in out.items() if not np.isfinite(p).all()]
+        if no_area:  # the kernels answer a surface without (finite) area with NaN points
+            raise ValueError(f"resample_n_points: the faces of {no_area} have no finite, positive area")
+        return out
 
 
 def bounding_box_corners(pts: np.ndarray) -> np.ndarray:

@@ -1430,3 +1430,91 @@ def det_match(iou: torch.Tensor, n_det, n_gt, gt_ignore, thresholds) -> Dict[str
                                      stream_ptr(dev)), "hp_det_match")
     out["det_ignore"] = out["det_ignore"].view(torch.bool)
     return out
+
+
+# ------------------------------------------------------------------------------------------- mesh resampling (mesh_sample.hip)
+MESH_SAMPLE_SCAN_CHUNK = 1024  # faces per step of the area scan (csrc/mesh_sample.hip: kScanChunk)
+
+
+def mesh_sample_workspace_bytes(n_obj: int, total_faces: int) -> int:
+    """``hp_mesh_sample_workspace_bytes``: ``8 (n_obj + total_faces)``."""
+    n = int(lib().hp_mesh_sample_workspace_bytes(int(n_obj), int(total_faces)))
+    assert n >= 0, "mesh_sample_workspace_bytes: n_obj >= 0 and 0 <= total_faces < 2^31"
+    return n
+
+
+def mesh_sample_surface_tables(vertices: torch.Tensor, faces: torch.Tensor, vert_offset: torch.Tensor, face_offset: torch.Tensor,
+                               n_samples: int, seed: int = 0) -> Dict[str, torch.Tensor]:
+    """``hp_mesh_sample_surface`` on explicit device tables: ``vertices [V_tot, 3]`` float32, ``faces [F_tot, 3]`` int32 (ids local
+    to their object), ``vert_offset`` / ``face_offset [n_obj + 1]`` int32.  Nothing is checked here: the kernels guard every
+    object (NaN points, ``face_id`` -1).  Returns ``points [n_obj, n_samples, 3]`` float32, ``face_id [n_obj, n_samples]`` int32
+    and ``area [n_obj]`` float64."""
+    dev = vertices.device
+    assert vertices.is_cuda and vertices.dtype == torch.float32 and vertices.dim() == 2 and vertices.shape[1] == 3, "vertices: [V, 3] float32 on the device"
+    assert faces.device == dev and faces.dtype == torch.int32 and faces.dim() == 2 and faces.shape[1] == 3, "faces: [F, 3] int32 on the device"
+    n_obj = vert_offset.numel() - 1
+    assert n_obj >= 0 and face_offset.numel() == n_obj + 1, "offsets: [n_obj + 1] each"
+    assert vert_offset.dtype == torch.int32 and face_offset.dtype == torch.int32 and vert_offset.device == dev and face_offset.device == dev
+    n_samples = int(n_samples)
+    assert n_samples >= 0, "mesh_sample_surface: negative n_samples"
+    out = {"points": torch.empty((n_obj, n_samples, 3), dtype=torch.float32, device=dev),
+           "face_id": torch.empty((n_obj, n_samples), dtype=torch.int32, device=dev),
+           "area": torch.empty((n_obj,), dtype=torch.float64, device=dev)}
+    if n_obj == 0 or n_samples == 0:
+        out["area"].fill_(float("nan"))  # nothing is launched: no area is computed
+        return out
+    nbytes = mesh_sample_workspace_bytes(n_obj, faces.shape[0])
+    ws = torch.empty(nbytes // 8, dtype=torch.float64, device=dev)
+    vertices, faces, vert_offset, face_offset = vertices.contiguous(), faces.contiguous(), vert_offset.contiguous(), face_offset.contiguous()
+    with torch.cuda.device(dev):
+        check(lib().hp_mesh_sample_surface(n_obj, ptr(vertices), ptr(faces), ptr(vert_offset), ptr(face_offset), n_samples,
+                                           int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out["points"]), ptr(out["face_id"]), ptr(out["area"]),
+                                           ptr(ws), nbytes, stream_ptr(dev)), "hp_mesh_sample_surface")
+    return out
+
+
+def mesh_sample_surface(vertices_list, faces_list, n_samples: int, seed: int = 0, return_face_ids: bool = False,
+                        return_areas: bool = False, device="cuda"):
+    """``n_samples`` points drawn uniformly from the surface of each mesh (``include/happypose_amd.h``, mesh surface resampling):
+    ``vertices_list[o] [V_o, 3]``, ``faces_list[o] [F_o, 3]``.  Object ``o`` of the random stream is the position in the lists.
+    The face indices are range-checked here, on the host, before any launch.  Returns ``points [n_obj, n_samples, 3]`` float32 on
+    the device, followed on request by ``face_ids [n_obj, n_samples]`` int32 and ``areas [n_obj]`` float64.  A mesh without faces
+    or without area gives NaN points and face id -1."""
+    assert len(vertices_list) == len(faces_list), "mesh_sample_surface: one face table per vertex table"
+    verts = [np.ascontiguousarray(np.asarray(v, dtype=np.float32).reshape(-1, 3)) for v in vertices_list]
+    faces = [np.ascontiguousarray(np.asarray(f).reshape(-1, 3)) for f in faces_list]
+    for o, (v, f) in enumerate(zip(verts, faces)):
+        if f.size:
+            lo, hi = int(f.min()), int(f.max())
+            assert 0 <= lo and hi < len(v), f"mesh_sample_surface: faces of object {o} in [{lo}, {hi}] index {len(v)} vertices"
+    voff = np.concatenate([[0], np.cumsum([len(v) for v in verts])]).astype(np.int64)
+    foff = np.concatenate([[0], np.cumsum([len(f) for f in faces])]).astype(np.int64)
+    assert voff[-1] < 2 ** 31 and foff[-1] < 2 ** 31, "mesh_sample_surface: tables of 2^31 rows or more"
+    dev = torch.device(device)
+    # one unused row closes each table, so that neither is ever empty (the offsets do not reach it)
+    v_all = np.concatenate(verts + [np.zeros((1, 3), np.float32)])
+    f_all = np.concatenate([f.astype(np.int32) for f in faces] + [np.zeros((1, 3), np.int32)])
+    out = mesh_sample_surface_tables(torch.as_tensor(v_all).to(dev), torch.as_tensor(f_all).to(dev), _i32(voff, dev), _i32(foff, dev),
+                                     n_samples, seed)
+    res = [out["points"]] + ([out["face_id"]] if return_face_ids else []) + ([out["area"]] if return_areas else [])
+    return res[0] if len(res) == 1 else tuple(res)
+
+
+def farthest_point_ids(points: torch.Tensor, counts, k: int) -> torch.Tensor:
+    """``hp_teaser_fps``: farthest-point sampling of ``points [n, n_max, 3]`` float32 on the device, set ``i`` holding
+    ``counts[i]`` points.  Starts at index 0, takes the point farthest from the chosen set, ties to the lowest index.  Returns
+    ``[n, k]`` int32: ``min(k, counts[i])`` indices in selection order, then -1."""
+    assert points.dim() == 3 and points.shape[2] == 3 and points.is_cuda, "points: [n, n_max, 3] on the device"
+    dev = points.device
+    n, n_max, k = points.shape[0], points.shape[1], int(k)
+    assert n_max >= 1 and k >= 1, "farthest_point_ids: n_max >= 1 and k >= 1"
+    counts = _i32(counts, dev)
+    assert counts.shape == (n,), "farthest_point_ids: one count per set"
+    points = _f32(points, dev)
+    idx = torch.empty((n, k), dtype=torch.int32, device=dev)
+    if n == 0:
+        return idx
+    scratch = torch.empty((n, n_max), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_teaser_fps(n, n_max, ptr(points), ptr(counts), k, ptr(scratch), ptr(idx), stream_ptr(dev)), "hp_teaser_fps")
+    return idx

@@ -948,6 +948,47 @@ int hp_det_match(int n_groups, const int32_t* d_n_det, const int32_t* d_n_gt, co
                  const uint8_t* d_gt_ignore, const float* d_thr, int n_thr, int32_t* d_det_match, uint8_t* d_det_ignore,
                  int32_t* d_gt_match, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Mesh surface resampling: the point table of MeshDataBase.batched(resample_n_points=N) (TB/lib3d/rigid_mesh_database.py:96-99,
+ * CP/lib3d/rigid_mesh_database.py:38-40) and of ModelNetErrorMeter.  The reference calls trimesh.sample.sample_surface; trimesh
+ * is not a dependency, so parity with it is UNPINNED and the definition below is the whole contract.  It is trimesh's documented
+ * algorithm (a face is picked with probability proportional to its area, the point is uniform in that face by the
+ * reflected-parallelogram rule) with two deliberate differences, marked (*).  csrc/mesh_sample.hip.
+ *
+ * Tables: the vertices (d_vertices [total_verts][3] float32) and faces (d_faces [total_faces][3] int32, indices LOCAL to their
+ * object) of all objects packed back to back; d_vert_offset / d_face_offset [n_obj + 1] int32 on the device give object o the rows
+ * offset[o] .. offset[o + 1].  With V and F the object's counts:
+ *  Areas and CDF   area_f = 0.5 |(v1 - v0) x (v2 - v0)| in fp64 from the fp32 vertices: e = v - v0 per component, the cross product
+ *                  as (ay bz - az by, az bx - ax bz, ax by - ay bx), the norm as sqrt((cx cx + cy cy) + cz cz), every operation
+ *                  rounded once (no fused multiply-add).  cum[f] = the inclusive prefix sum in fp64, in a FIXED order: one
+ *                  workgroup per object, chunks of 1024 faces in sequence with a carried prefix (wavefront scan, wave totals added
+ *                  in wave order).  No atomics, bit-identical from run to run; it differs from the sequential sum by rounding
+ *                  only (about F 2^-53 relative).  total = cum[F - 1] goes to d_area [n_obj] (may be NULL).
+ *  Random numbers  sample i of object o draws Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53, 0xCD9E8D57, key
+ *                  increments 0x9E3779B9, 0xBB67AE85) with key (seed & 0xffffffff, seed >> 32) and counter (i, o, 0, 0), giving
+ *                  r0..r3.  Stateless: a sample does not depend on n_samples, on n_obj or on the other objects of the call.
+ *  Face pick       u = ((uint64)r0 << 21 | r1 >> 11) 2^-53,  pick = u total  in fp64; the face is the first f with cum[f] > pick
+ *                  (STRICT), by binary search, clamped to F - 1.
+ *                  (*) trimesh uses searchsorted(side="left") (cum[f] >= pick): the strict rule never picks a zero-area face,
+ *                  except through the clamp.
+ *  Point           ia = r2 >> 8, ib = r3 >> 8 (24-bit integers); if ia + ib > 2^24 both become 2^24 - i -- (*) compared on the
+ *                  integers: trimesh's float a + b > 1 may round; a = ia 2^-24, b = ib 2^-24 (exact in fp32);
+ *                  p = (v0 + a (v1 - v0)) + b (v2 - v0)  per component in fp32, every operation rounded once.
+ *                  d_points [n_obj][n_samples][3], d_face_id [n_obj][n_samples] (object-local, may be NULL).
+ *  Guards          an object with no faces, total == 0, a non-finite total, a face index outside 0 .. V - 1, or offsets that are
+ *                  negative, descend or pass the table the workspace was sized for gives NaN points and face_id -1 for all its
+ *                  samples (d_area: the total, NaN for bad indices or offsets).  Such an object reads nothing outside the tables:
+ *                  a face with a bad index reads no vertex.  Its neighbours in the call are unaffected.
+ * n_obj == 0 or n_samples == 0 returns HP_OK and launches nothing.  At most 65535 objects per call, total_faces < 2^31.
+ * d_workspace: hp_mesh_sample_workspace_bytes(n_obj, total_faces) = 8 (n_obj + total_faces) bytes, 8-byte aligned (-1 for sizes
+ * out of range): the totals and the CDF.  Two kernels (areas + scan, then one thread per (object, sample)), wave64, no
+ * floating-point atomics; not used on the render-and-compare path.
+ * ---------------------------------------------------------------------------------- */
+int64_t hp_mesh_sample_workspace_bytes(int n_obj, int64_t total_faces);
+int hp_mesh_sample_surface(int n_obj, const float* d_vertices, const int32_t* d_faces, const int32_t* d_vert_offset,
+                           const int32_t* d_face_offset, int n_samples, uint64_t seed, float* d_points, int32_t* d_face_id,
+                           double* d_area, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

@@ -169,6 +169,14 @@ _PROTOS = {
     "hp_pose_errors": (C.c_int, [C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, c_f32p, C.c_int, c_f32p, C.c_int, c_f32p, c_f32p, c_f32p,
                                  c_i32p, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_i32p,
                                  C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_pose_loss_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "hp_loss_co_symmetric": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, C.c_void_p, C.c_int64,
+                                       C.c_void_p]),
+    "hp_loss_co_symmetric_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, C.c_void_p]),
+    "hp_loss_refiner_disentangled": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p,
+                                               c_i32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_loss_refiner_disentangled_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p,
+                                                        c_f32p, c_f32p, c_f32p, C.c_void_p]),
     "hp_scene_compose": (C.c_int, [C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, c_i32p,
                                    c_u8p, C.c_void_p]),
     "hp_scene_visibility": (C.c_int, [C.c_int, c_i32p, C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, c_i32p, C.c_void_p]),

@@ -1140,6 +1140,98 @@ def pose_errors(pred_id, gt_id, obj_id, mode, poses_pred: torch.Tensor, poses_gt
                               return_assign=return_assign)
 
 
+# ---- training / validation losses (csrc/pose_losses.hip) -----------------------------------------------------------------------
+POSE_LOSS_SYM_CHUNK = 8  # HP_POSE_LOSS_SYM_CHUNK
+
+
+def _loss_tables(what: str, TCO_possible_gt: torch.Tensor, points: torch.Tensor, **per_row: Tuple[torch.Tensor, tuple]):
+    """Shapes as the reference asserts them; float32 contiguous device tensors back (there is no CPU path)."""
+    assert TCO_possible_gt.dim() == 4 and TCO_possible_gt.shape[-2:] == (4, 4), f"{what}: TCO_possible_gt [B, S, 4, 4]"
+    b, s = TCO_possible_gt.shape[:2]
+    assert points.dim() == 3 and points.shape[0] == b and points.shape[-1] == 3, f"{what}: points [B, N, 3]"
+    tensors = {"TCO_possible_gt": TCO_possible_gt, "points": points}
+    for name, (t, shape) in per_row.items():
+        if t is not None:
+            assert tuple(t.shape) == (b, *shape), f"{what}: {name} {[b, *shape]}"
+            tensors[name] = t
+    dev = points.device
+    for name, t in tensors.items():
+        if not t.is_cuda or t.device != dev:
+            raise ValueError(f"{what}: {name} is on {t.device}; every input lives on one GPU (happypose_amd has no CPU path)")
+    return b, s, points.shape[1], {name: _f32(t, dev) for name, t in tensors.items()}
+
+
+def _loss_workspace(b: int, s: int, dev) -> Tuple[torch.Tensor, int]:
+    nbytes = int(lib().hp_pose_loss_workspace_bytes(b, max(s, 1)))
+    return torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev), nbytes
+
+
+def loss_co_symmetric_forward(TCO_possible_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor):
+    """``hp_loss_co_symmetric``: ``(loss [B], sym_id [B] int32, TCO_assign [B, 4, 4])``."""
+    b, s, n, t = _loss_tables("loss_CO_symmetric", TCO_possible_gt, points, TCO_pred=(TCO_pred, (4, 4)))
+    dev = t["points"].device
+    loss = torch.empty(b, dtype=torch.float32, device=dev)
+    sym_id = torch.empty(b, dtype=torch.int32, device=dev)
+    assign = torch.empty(b, 4, 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        ws, nbytes = _loss_workspace(b, s, dev)
+        check(lib().hp_loss_co_symmetric(b, s, n, ptr(t["TCO_possible_gt"]), ptr(t["TCO_pred"]), ptr(t["points"]), ptr(loss), ptr(sym_id),
+                                         ptr(assign), ptr(ws), nbytes, stream_ptr(dev)), "hp_loss_co_symmetric")
+    return loss, sym_id, assign
+
+
+def loss_co_symmetric_backward(TCO_possible_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor, sym_id: torch.Tensor,
+                               grad_loss: torch.Tensor) -> torch.Tensor:
+    """``hp_loss_co_symmetric_backward``: the gradient with respect to ``TCO_pred`` ``[B, 4, 4]`` (last row zero)."""
+    b, s, n, t = _loss_tables("loss_CO_symmetric", TCO_possible_gt, points, TCO_pred=(TCO_pred, (4, 4)), grad_loss=(grad_loss, ()))
+    dev = t["points"].device
+    assert sym_id.shape == (b,) and sym_id.dtype == torch.int32 and sym_id.device == dev
+    grad = torch.empty(b, 4, 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_loss_co_symmetric_backward(b, s, n, ptr(t["TCO_possible_gt"]), ptr(t["TCO_pred"]), ptr(t["points"]),
+                                                  ptr(sym_id.contiguous()), ptr(t["grad_loss"]), ptr(grad), stream_ptr(dev)),
+              "hp_loss_co_symmetric_backward")
+    return grad
+
+
+def loss_refiner_forward(TCO_possible_gt: torch.Tensor, TCO_input: torch.Tensor, refiner_outputs: torch.Tensor, K_crop: torch.Tensor,
+                         points: torch.Tensor, tCR: Optional[torch.Tensor] = None):
+    """``hp_loss_refiner_disentangled`` (``tCR=None``: CosyPose's form): ``(loss [B], parts [B, 3] = orn, xy, z, sym_ids [B, 3]
+    int32)``."""
+    b, s, n, t = _loss_tables("loss_refiner_CO_disentangled", TCO_possible_gt, points, TCO_input=(TCO_input, (4, 4)),
+                              refiner_outputs=(refiner_outputs, (9,)), K_crop=(K_crop, (3, 3)), tCR=(tCR, (3,)))
+    dev = t["points"].device
+    loss = torch.empty(b, dtype=torch.float32, device=dev)
+    parts = torch.empty(b, 3, dtype=torch.float32, device=dev)
+    sym_ids = torch.empty(b, 3, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        ws, nbytes = _loss_workspace(b, s, dev)
+        check(lib().hp_loss_refiner_disentangled(b, s, n, ptr(t["TCO_possible_gt"]), ptr(t["TCO_input"]), ptr(t["refiner_outputs"]),
+                                                 ptr(t["K_crop"]), ptr(t["points"]), ptr(t.get("tCR")), ptr(loss), ptr(parts),
+                                                 ptr(sym_ids), ptr(ws), nbytes, stream_ptr(dev)), "hp_loss_refiner_disentangled")
+    return loss, parts, sym_ids
+
+
+def loss_refiner_backward(TCO_possible_gt: torch.Tensor, TCO_input: torch.Tensor, refiner_outputs: torch.Tensor, K_crop: torch.Tensor,
+                          points: torch.Tensor, tCR: Optional[torch.Tensor], sym_ids: torch.Tensor, grad_loss: torch.Tensor,
+                          return_parts: bool = False):
+    """``hp_loss_refiner_disentangled_backward``: the gradient with respect to ``refiner_outputs`` ``[B, 9]``; with
+    ``return_parts`` also the same gradient split by term ``[B, 3, 9]``."""
+    b, s, n, t = _loss_tables("loss_refiner_CO_disentangled", TCO_possible_gt, points, TCO_input=(TCO_input, (4, 4)),
+                              refiner_outputs=(refiner_outputs, (9,)), K_crop=(K_crop, (3, 3)), tCR=(tCR, (3,)),
+                              grad_loss=(grad_loss, ()))
+    dev = t["points"].device
+    assert sym_ids.shape == (b, 3) and sym_ids.dtype == torch.int32 and sym_ids.device == dev
+    grad = torch.empty(b, 9, dtype=torch.float32, device=dev)
+    grad_parts = torch.empty(b, 3, 9, dtype=torch.float32, device=dev) if return_parts else None
+    with torch.cuda.device(dev):
+        check(lib().hp_loss_refiner_disentangled_backward(b, s, n, ptr(t["TCO_possible_gt"]), ptr(t["TCO_input"]),
+                                                          ptr(t["refiner_outputs"]), ptr(t["K_crop"]), ptr(t["points"]), ptr(t.get("tCR")),
+                                                          ptr(sym_ids.contiguous()), ptr(t["grad_loss"]), ptr(grad), ptr(grad_parts),
+                                                          stream_ptr(dev)), "hp_loss_refiner_disentangled_backward")
+    return (grad, grad_parts) if return_parts else grad
+
+
 # --------------------------------------------------------------------------------------------------------------- scenes (scene.hip)
 SCENE_VIS_FIELDS = 10  # HP_SCENE_VIS_FIELDS
 SCENE_MAX_DILATE = 3   # HP_SCENE_MAX_DILATE

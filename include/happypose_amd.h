@@ -802,7 +802,64 @@ int hp_pose_errors(int n_rows, const int32_t* d_pred_id, const int32_t* d_gt_id,
                    void* stream);
 
 /* ------------------------------------------------------------------------------------
- * Multi-object scenes: Panda3dSceneRenderer.render_scene(object_datas, camera_datas, light_datas, ...)
+ * The losses the pose networks are trained and validated on, value and gradient: loss_CO_symmetric
+ * (TB/lib3d/cosypose_ops.py:65-79 = CP/lib3d/cosypose_ops.py:45-59), compute_ADD_L1_loss (TB/lib3d/mesh_losses.py:39-48),
+ * loss_refiner_CO_disentangled (CP/lib3d/cosypose_ops.py:62-101) and loss_refiner_CO_disentangled_reference_point
+ * (TB/lib3d/cosypose_ops.py:82-156), the validation figure loss_TCO-iter=k of the reference's trainers.  csrc/pose_losses.hip.
+ * There is no trainer here: this is the loss layer.
+ *
+ * Row b of B holds d_TCO_possible_gt [b][n_sym][16] (entry 0 is the ground truth) and d_points [b][n_pts][3].
+ * The symmetric loss of a pose T_pred: for every symmetry s, l_s = mean over the points j and the three components of
+ * |T_pred p_j - T_gt,s p_j|; the loss is min_s l_s and the chosen s the lowest index on an exact tie.  compute_ADD_L1_loss is the
+ * same with n_sym = 1.  hp_loss_co_symmetric writes d_loss [b], d_sym_id [b] and, unless NULL, d_TCO_assign [b][16] = the chosen
+ * T_gt,s.
+ * The disentangled refiner loss of the network's 9-D update o (d_refiner_outputs [b][9]: 6-D rotation, vx vy, vz) at the input
+ * pose d_TCO_input [b][16] with the crop's intrinsics d_K_crop [b][9] (fx = K[0], fy = K[4]) is the sum of three symmetric losses,
+ * each with its own minimum over s, of three poses that are the ground truth T_gt = T_gt,0 except for
+ *   orientation  the rotation dR R_in, dR = compute_rotation_matrix_from_ortho6d(o[0:6]) (Gram-Schmidt, no epsilon)
+ *   xy           t_x, t_y of the update applied with the ground truth's rotation update and depth ratio
+ *   z            t_z of the update applied with the ground truth's rotation update.
+ * d_tCR == NULL, CosyPose's image-space update: t_xy = (o[6:8] / fxfy + t_in,xy / t_in,z) t_gt,z and t_z = o[8] t_in,z.
+ * d_tCR [b][3], MegaPose's update about the reference point: with dR_gt = R_gt R_in^T, q = dR_gt (t_in - tCR) and
+ * vz_gt = (t_gt,z - q_z) / tCR_z: t_xy = q_xy + (o[6:8] / fxfy + tCR_xy / tCR_z) vz_gt tCR_z and t_z = q_z + o[8] tCR_z (the
+ * reference's vxvy_gt reaches none of the three poses).
+ * hp_loss_refiner_disentangled writes d_loss [b] = orn + xy + z, d_loss_parts [b][3] = (loss_orn, loss_xy, loss_z) and
+ * d_sym_ids [b][3], the symmetry each term chose.
+ *
+ * Gradients: of the symmetric loss with respect to the upper 3 x 4 of T_pred (d_grad_TCO_pred [b][16], last row zero), of the
+ * refiner loss with respect to o only (d_grad_outputs [b][9]; the reference detaches TCO_input between iterations, the rest is
+ * data), both multiplied by the row's upstream gradient d_grad_loss [b].  The gradient flows through the chosen symmetry only
+ * (d_sym_id / d_sym_ids as the forward call wrote them), d|x|/dx = sign(x) with sign(0) = 0, the orientation term chains
+ * through the Gram-Schmidt, the xy term reaches o[6], o[7] only and the z term o[8] only.  d_grad_parts [b][3][9] (may be NULL)
+ * receives the same gradient split by term.
+ *
+ * The points are transformed in float32; the predicted poses and every sum are formed in double and rounded once.  A term loss
+ * that is not finite -- a non-finite point, pose, intrinsic or update, a degenerate 6-D part -- makes every float output of the row
+ * NaN and its ids -1, and the backward call answers ids outside 0..n_sym-1 with a NaN gradient row; other rows are untouched.
+ * b == 0 returns HP_OK and launches nothing; n_sym < 1 or n_pts < 1 is HP_ERR_ARG.  A workgroup is one (row, chunk of
+ * HP_POSE_LOSS_SYM_CHUNK symmetries); the per-(row, symmetry, term) means go to d_workspace (hp_pose_loss_workspace_bytes(b,
+ * n_sym) bytes = b x n_sym x 12, nothing of size b x n_sym x n_pts) and a second launch takes the minima.  The backward calls
+ * need no workspace.  No atomics: a row's outputs do not depend on the other rows of the call and are bit-identical from run to run.
+ * ---------------------------------------------------------------------------------- */
+#define HP_POSE_LOSS_SYM_CHUNK 8
+int64_t hp_pose_loss_workspace_bytes(int b, int n_sym);
+int hp_loss_co_symmetric(int b, int n_sym, int n_pts, const float* d_TCO_possible_gt, const float* d_TCO_pred, const float* d_points,
+                         float* d_loss, int32_t* d_sym_id, float* d_TCO_assign, void* d_workspace, int64_t workspace_bytes,
+                         void* stream);
+int hp_loss_co_symmetric_backward(int b, int n_sym, int n_pts, const float* d_TCO_possible_gt, const float* d_TCO_pred,
+                                  const float* d_points, const int32_t* d_sym_id, const float* d_grad_loss, float* d_grad_TCO_pred,
+                                  void* stream);
+int hp_loss_refiner_disentangled(int b, int n_sym, int n_pts, const float* d_TCO_possible_gt, const float* d_TCO_input,
+                                 const float* d_refiner_outputs, const float* d_K_crop, const float* d_points,
+                                 const float* d_tCR /* [b][3] or NULL */, float* d_loss, float* d_loss_parts, int32_t* d_sym_ids,
+                                 void* d_workspace, int64_t workspace_bytes, void* stream);
+int hp_loss_refiner_disentangled_backward(int b, int n_sym, int n_pts, const float* d_TCO_possible_gt, const float* d_TCO_input,
+                                          const float* d_refiner_outputs, const float* d_K_crop, const float* d_points,
+                                          const float* d_tCR /* [b][3] or NULL */, const int32_t* d_sym_ids,
+                                          const float* d_grad_loss, float* d_grad_outputs, float* d_grad_parts, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Multi-object scenes:Panda3dSceneRenderer.render_scene(object_datas, camera_datas, light_datas, ...)
  * (TB/renderer/panda3d_scene_renderer.py:320-390), the gt-info quantities of MP/scripts/bop_calc_gt_info.py (px_count_all,
  * px_count_visib, bbox_obj, bbox_visib), make_contour_overlay (TB/visualization/utils.py:54-82) and BokehPlotter.plot_overlay
  * (TB/visualization/bokeh_plotter.py:116-141).  csrc/scene.hip.

@@ -195,6 +195,19 @@ _PROTOS = {
     "hp_mesh_sample_workspace_bytes": (C.c_int64, [C.c_int, C.c_int64]),
     "hp_mesh_sample_surface": (C.c_int, [C.c_int, c_f32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_uint64, c_f32p, c_i32p, C.c_void_p,
                                          C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_aug_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int, C.c_int]),
+    "hp_aug_rgb_enhance": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_i32p, c_f32p, c_u8p, c_u8p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_aug_rgb_blur": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_i32p, C.c_void_p, C.c_void_p, c_u8p, c_u8p, C.c_int, C.c_void_p,
+                                  C.c_int64, C.c_void_p]),
+    "hp_aug_replace_background": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_i32p, c_u8p, c_u8p, c_u8p, C.c_void_p]),
+    "hp_aug_depth_noise": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_i32p, c_i32p, c_u8p, C.c_uint64, c_f32p,
+                                     C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_aug_depth_missing": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, C.c_void_p, c_u8p, C.c_uint64, c_f32p, C.c_void_p, C.c_int64,
+                                       C.c_void_p]),
+    "hp_aug_depth_ellipses": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_i32p, C.c_int, C.c_int, c_u8p, c_f32p, C.c_void_p,
+                                        C.c_int64, C.c_void_p]),
+    "hp_aug_depth_blur": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, C.c_int, c_u8p, c_f32p, C.c_void_p]),
+    "hp_aug_depth_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, c_u8p, c_f32p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

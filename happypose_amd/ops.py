@@ -1610,3 +1610,229 @@ def farthest_point_ids(points: torch.Tensor, counts, k: int) -> torch.Tensor:
     with torch.cuda.device(dev):
         check(lib().hp_teaser_fps(n, n_max, ptr(points), ptr(counts), k, ptr(scratch), ptr(idx), stream_ptr(dev)), "hp_teaser_fps")
     return idx
+
+
+# ------------------------------------------------------------------------------------ training-image augmentations (augment.hip)
+AUG_OPS = {"brightness": 0, "color": 1, "contrast": 2, "sharpness": 3}  # HP_AUG_OP_*
+
+
+def _aug_frames(t: torch.Tensor, what: str, dtype, channels: bool) -> torch.Tensor:
+    """A dense batch on the device: ``[B, H, W, 3]`` uint8 or ``[B, H, W]`` of ``dtype``.  A CPU tensor raises ValueError: there is
+    no host implementation and none is substituted."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{what}: a tensor on the device is required (no CPU implementation)")
+    if t.dtype != dtype or t.dim() != (4 if channels else 3) or (channels and t.shape[-1] != 3) or not t.is_contiguous():
+        raise ValueError(f"{what}: dense {'[B, H, W, 3]' if channels else '[B, H, W]'} {dtype} expected, got {tuple(t.shape)} {t.dtype}")
+    if t.shape[1] < 1 or t.shape[2] < 1:
+        raise ValueError(f"{what}: empty frames")
+    return t
+
+
+def _aug_param(v, n: int, dtype, dev, what: str) -> torch.Tensor:
+    """A per-image parameter: a scalar or ``n`` values, as a device array of ``dtype``.  The caller holds the result in a local
+    until the call is enqueued: a temporary would hand its block back to the allocator, and the next parameter would land on it."""
+    t = torch.as_tensor(v).to(dtype).reshape(-1)
+    if t.numel() == 1 and n != 1:
+        t = t.expand(n)
+    if t.numel() != n:
+        raise ValueError(f"{what}: one value per image ({n}), got {t.numel()}")
+    return t.contiguous().to(dev)
+
+
+def _aug_apply(apply, n: int, dev) -> torch.Tensor:
+    return _aug_param(True if apply is None else apply, n, torch.bool, dev, "apply").view(torch.uint8)
+
+
+def _aug_out(x: torch.Tensor, out: Optional[torch.Tensor], in_place_ok: bool, what: str) -> torch.Tensor:
+    if out is None:
+        return torch.empty_like(x)
+    if out.shape != x.shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError(f"{what}: out must match the input")
+    if not in_place_ok and out.data_ptr() == x.data_ptr():
+        raise ValueError(f"{what}: reads a neighbourhood, out must not alias the input")
+    return out
+
+
+def aug_workspace(B: int, h: int, w: int, max_ellipses: int, dev) -> Tuple[torch.Tensor, int]:
+    """``hp_aug_workspace_bytes`` and a buffer of that size (8-byte aligned)."""
+    n = int(lib().hp_aug_workspace_bytes(int(B), int(h), int(w), int(max_ellipses)))
+    if n < 0:
+        raise ValueError("augmentations: at most 65535 frames of at most 2^28 pixels")
+    return torch.empty(max(n // 8, 1), dtype=torch.int64, device=dev), n
+
+
+def aug_rgb_enhance(rgb: torch.Tensor, op, factor, apply=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_aug_rgb_enhance``: Pillow's ``ImageEnhance`` per image.  ``op`` names (``AUG_OPS``) or codes and ``factor``: a scalar or
+    one per image; ``apply [B]`` bool (default all).  Not in place."""
+    rgb = _aug_frames(rgb, "aug_rgb_enhance: rgb", torch.uint8, True)
+    B, h, w, dev = rgb.shape[0], rgb.shape[1], rgb.shape[2], rgb.device
+    out = _aug_out(rgb, out, False, "aug_rgb_enhance")
+    if B == 0:
+        return out
+    codes = [op] if isinstance(op, (str, int)) else list(op)
+    codes = [AUG_OPS[c] if isinstance(c, str) else int(c) for c in codes]
+    ws, nbytes = aug_workspace(B, h, w, 0, dev)
+    _p0 = _aug_param(codes, B, torch.int32, dev, "op")
+    _p1 = _aug_param(factor, B, torch.float32, dev, "factor")
+    _p2 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_aug_rgb_enhance(B, h, w, ptr(rgb), ptr(_p0),
+                                       ptr(_p1), ptr(_p2), ptr(out),
+                                       ptr(ws), nbytes, stream_ptr(dev)), "hp_aug_rgb_enhance")
+    return out
+
+
+def aug_blur_params(k) -> Tuple[int, int, int]:
+    """``(r, ww, fw)`` of the box filter whose three passes stand for Pillow's Gaussian blur of radius ``k``: float32, as the
+    header writes it."""
+    f32 = np.float32
+    sigma2 = f32(f32(f32(k) * f32(k)) / f32(3))
+    L = f32(np.sqrt(12.0 * float(sigma2) + 1.0))
+    l = f32(np.floor((float(L) - 1.0) / 2.0))
+    a = f32(f32(f32(2) * l + f32(1)) * f32(f32(l * f32(l + f32(1))) - f32(f32(3) * sigma2)))
+    a = f32(a / f32(f32(6) * f32(sigma2 - f32(f32(l + f32(1)) * f32(l + f32(1))))))
+    r_f = f32(l + a)
+    r = int(r_f)
+    ww = int(f32(f32(1 << 24) / f32(f32(r_f * f32(2)) + f32(1))))
+    return r, ww, ((1 << 24) - (2 * r + 1) * ww) // 2
+
+
+def aug_rgb_blur(rgb: torch.Tensor, radius, apply=None, out: Optional[torch.Tensor] = None, force_general: bool = False) -> torch.Tensor:
+    """``hp_aug_rgb_blur``: Pillow's ``GaussianBlur(k)`` with ``k = radius`` (a positive number, scalar or one per image).
+    ``force_general`` takes the one-launch-per-pass path whatever the frame size (same bytes).  Not in place."""
+    rgb = _aug_frames(rgb, "aug_rgb_blur: rgb", torch.uint8, True)
+    B, h, w, dev = rgb.shape[0], rgb.shape[1], rgb.shape[2], rgb.device
+    out = _aug_out(rgb, out, False, "aug_rgb_blur")
+    if B == 0:
+        return out
+    ks = np.broadcast_to(np.asarray(radius, np.float64).reshape(-1), (B,)) if np.size(radius) in (1, B) else None
+    if ks is None or not (ks > 0).all():
+        raise ValueError("aug_rgb_blur: one positive radius per image")
+    par = np.array([aug_blur_params(k) for k in ks], np.int64).reshape(B, 3)
+    ws, nbytes = aug_workspace(B, h, w, 0, dev)
+    _p0 = _aug_param(par[:, 0], B, torch.int32, dev, "radius")
+    _p1 = _aug_param(par[:, 1], B, torch.int32, dev, "ww")
+    _p2 = _aug_param(par[:, 2], B, torch.int32, dev, "fw")
+    _p3 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_aug_rgb_blur(B, h, w, ptr(rgb), ptr(_p0),
+                                    ptr(_p1), ptr(_p2),
+                                    ptr(_p3), ptr(out), int(bool(force_general)), ptr(ws), nbytes, stream_ptr(dev)),
+              "hp_aug_rgb_blur")
+    return out
+
+
+def _aug_seg(seg: torch.Tensor, like: torch.Tensor, what: str) -> torch.Tensor:
+    seg = _aug_frames(seg, what, torch.int32, False)
+    if seg.shape != like.shape[:3] or seg.device != like.device:
+        raise ValueError(f"{what}: [B, H, W] of the frames")
+    return seg
+
+
+def aug_replace_background(rgb: torch.Tensor, segmentation: torch.Tensor, background: torch.Tensor, apply=None,
+                           out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_aug_replace_background``: ``background`` where ``segmentation == 0``.  May run in place (``out=rgb``)."""
+    rgb = _aug_frames(rgb, "aug_replace_background: rgb", torch.uint8, True)
+    background = _aug_frames(background, "aug_replace_background: background", torch.uint8, True)
+    seg = _aug_seg(segmentation, rgb, "aug_replace_background: segmentation")
+    if background.shape != rgb.shape or background.device != rgb.device:
+        raise ValueError("aug_replace_background: background must already have the frames' size")
+    B, h, w, dev = rgb.shape[0], rgb.shape[1], rgb.shape[2], rgb.device
+    out = _aug_out(rgb, out, True, "aug_replace_background")
+    if B:
+        _p0 = _aug_apply(apply, B, dev)
+        with torch.cuda.device(dev):
+            check(lib().hp_aug_replace_background(B, h, w, ptr(rgb), ptr(seg), ptr(background), ptr(_p0), ptr(out),
+                                                  stream_ptr(dev)), "hp_aug_replace_background")
+    return out
+
+
+def _aug_depth(depth: torch.Tensor, out, in_place_ok: bool, what: str):
+    depth = _aug_frames(depth, f"{what}: depth", torch.float32, False)
+    return depth, _aug_out(depth, out, in_place_ok, what), depth.shape[0], depth.shape[1], depth.shape[2], depth.device
+
+
+def aug_depth_noise(depth: torch.Tensor, std, seed: int, grid=None, apply=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_aug_depth_noise``: Gaussian noise of ``std`` on the valid pixels; with ``grid = (grid_h, grid_w)`` (scalars or one per
+    image) the noise is drawn on that grid and upsampled bicubically.  May run in place."""
+    depth, out, B, h, w, dev = _aug_depth(depth, out, True, "aug_depth_noise")
+    if B == 0:
+        return out
+    gh = gw = ws = None
+    nbytes = 0
+    if grid is not None:
+        gh, gw = _aug_param(grid[0], B, torch.int32, dev, "grid_h"), _aug_param(grid[1], B, torch.int32, dev, "grid_w")
+        ws, nbytes = aug_workspace(B, h, w, 0, dev)
+    _p0 = _aug_param(std, B, torch.float32, dev, "std")
+    _p1 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_aug_depth_noise(B, h, w, ptr(depth), ptr(_p0), int(grid is not None), ptr(gh),
+                                       ptr(gw), ptr(_p1), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), ptr(ws), nbytes,
+                                       stream_ptr(dev)), "hp_aug_depth_noise")
+    return out
+
+
+def aug_depth_missing(depth: torch.Tensor, fraction, seed: int, apply=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_aug_depth_missing``: exactly ``int(fraction * n_valid)`` of an image's valid pixels become 0.  May run in place."""
+    depth, out, B, h, w, dev = _aug_depth(depth, out, True, "aug_depth_missing")
+    if B == 0:
+        return out
+    ws, nbytes = aug_workspace(B, h, w, 0, dev)
+    _p0 = _aug_param(fraction, B, torch.float64, dev, "fraction")
+    _p1 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_aug_depth_missing(B, h, w, ptr(depth), ptr(_p0),
+                                         ptr(_p1), int(seed) & 0xFFFFFFFFFFFFFFFF, ptr(out), ptr(ws), nbytes,
+                                         stream_ptr(dev)), "hp_aug_depth_missing")
+    return out
+
+
+def aug_depth_ellipses(depth: torch.Tensor, table, count, noise: bool, apply=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_aug_depth_ellipses``: ``table [B, E, 5]`` = (u, rx, ry, angle_deg, value), ``count [B]``.  ``noise=False`` zeroes the
+    pixels inside, ``noise=True`` adds the last covering ellipse's value to the valid ones.  May run in place."""
+    depth, out, B, h, w, dev = _aug_depth(depth, out, True, "aug_depth_ellipses")
+    if B == 0:
+        return out
+    table = torch.as_tensor(table).to(torch.float32)
+    if table.dim() != 3 or table.shape[0] != B or table.shape[2] != 5:
+        raise ValueError("aug_depth_ellipses: table [B, E, 5]")
+    E = table.shape[1]
+    table = table.contiguous().to(dev) if E else None
+    ws, nbytes = aug_workspace(B, h, w, E, dev)
+    _p0 = _aug_param(count, B, torch.int32, dev, "count")
+    _p1 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_aug_depth_ellipses(B, h, w, ptr(depth), ptr(table), ptr(_p0), E,
+                                          int(bool(noise)), ptr(_p1), ptr(out), ptr(ws), nbytes, stream_ptr(dev)),
+              "hp_aug_depth_ellipses")
+    return out
+
+
+def aug_depth_blur(depth: torch.Tensor, ksize, apply=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_aug_depth_blur``: the ``k x k`` box filter, ``k = ksize`` (scalar or one per image, each >= 1).  A frame side shorter
+    than the largest ``k`` raises AssertionError (the library's argument error) and launches nothing.  Not in place."""
+    depth, out, B, h, w, dev = _aug_depth(depth, out, False, "aug_depth_blur")
+    if B == 0:
+        return out
+    ks = np.asarray(ksize, np.int64).reshape(-1)
+    if ks.size not in (1, B) or (ks < 1).any():
+        raise ValueError("aug_depth_blur: one k >= 1 per image")
+    _p0 = _aug_param(ks, B, torch.int32, dev, "ksize")
+    _p1 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_aug_depth_blur(B, h, w, ptr(depth), ptr(_p0), int(ks.max()),
+                                      ptr(_p1), ptr(out), stream_ptr(dev)), "hp_aug_depth_blur")
+    return out
+
+
+def aug_depth_mask(depth: torch.Tensor, segmentation: Optional[torch.Tensor] = None, apply=None,
+                   out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_aug_depth_mask``: all zeros without ``segmentation``, else zero where ``segmentation == 0``.  May run in place."""
+    depth, out, B, h, w, dev = _aug_depth(depth, out, True, "aug_depth_mask")
+    seg = None if segmentation is None else _aug_seg(segmentation, depth, "aug_depth_mask: segmentation")
+    if B:
+        _p0 = _aug_apply(apply, B, dev)
+        with torch.cuda.device(dev):
+            check(lib().hp_aug_depth_mask(B, h, w, ptr(depth), ptr(seg), ptr(_p0), ptr(out), stream_ptr(dev)),
+                  "hp_aug_depth_mask")
+    return out

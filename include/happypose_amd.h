@@ -1046,6 +1046,112 @@ int hp_mesh_sample_surface(int n_obj, const float* d_vertices, const int32_t* d_
                            const int32_t* d_face_offset, int n_samples, uint64_t seed, float* d_points, int32_t* d_face_id,
                            double* d_area, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Training-image augmentations: the transforms of the reference's toolbox/datasets/augmentations.py on a whole batch of frames
+ * that already lives on the device.  csrc/augment.hip; the user-facing layer is happypose_amd/augmentations.py.
+ *
+ * Tensors are dense: d_rgb / d_background / d_out [B][h][w][3] uint8; d_depth [B][h][w] float32 in metres, 0 = invalid;
+ * d_segmentation [B][h][w] int32, 0 = background.  Every per-image parameter is a DEVICE array of length B; d_apply [B] uint8:
+ * an image with d_apply[b] == 0 comes back bit for bit.  The result for image b does not depend on the other images or on B.
+ * There are no floating-point atomics: results are bit-identical from run to run.  B == 0 returns HP_OK and launches nothing;
+ * a null pointer, h <= 0, w <= 0, B > 65535 or h w > 2^28 is HP_ERR_ARG before the GPU is touched.
+ * IN PLACE (d_out == d_rgb / d_depth) is allowed for hp_aug_replace_background, hp_aug_depth_noise, hp_aug_depth_missing,
+ * hp_aug_depth_ellipses and hp_aug_depth_mask; hp_aug_rgb_enhance, hp_aug_rgb_blur and hp_aug_depth_blur read a neighbourhood and
+ * answer HP_ERR_ARG when d_out aliases the input.
+ * d_workspace: hp_aug_workspace_bytes(B, h, w, max_ellipses) = 8 B + roundup8(4 B h w) + 32 B max_ellipses bytes, 8-byte aligned
+ * (-1 for sizes out of range); max_ellipses is 0 for every call but hp_aug_depth_ellipses.  hp_aug_replace_background,
+ * hp_aug_depth_blur, hp_aug_depth_mask and uncorrelated hp_aug_depth_noise use none.
+ *
+ * RGB: Pillow's arithmetic, matched byte for byte (pinned against Pillow 12.2 by tests/golden/g14_augmentations.npz).
+ *   blend(a, x, f)   per byte in float32, every operation rounded once (no fused multiply-add): t = a + f (x - a).  For
+ *                    0 <= f <= 1 the result is (uint8) t, truncated; otherwise t <= 0 gives 0, t >= 255 gives 255, else truncated.
+ *   gray             (R 19595 + G 38470 + B 7471 + 0x8000) >> 16.
+ *   hp_aug_rgb_enhance, d_op[b] one of HP_AUG_OP_* (any other value leaves the image unchanged), d_factor[b] = f:
+ *     BRIGHTNESS     blend(0, x, f)
+ *     COLOR          blend(gray, x, f), the pixel's gray in all three channels
+ *     CONTRAST       blend(m, x, f), m = (int)(sum(gray) / (double)(h w) + 0.5): one scalar per image; the sum is an exact 64-bit
+ *                    integer (integer atomics, one per workgroup), the division is done in double
+ *     SHARPNESS      blend(smooth(x), x, f); smooth is Pillow's SMOOTH: the 3 x 3 kernel (1,1,1,1,5,1,1,1,1), each tap the float32
+ *                    of k / 13, accumulated in float32 onto an initial 0.5 -- row y + 1 first, then y, then y - 1, each from left to
+ *                    right, every product and sum rounded once -- then floor and clip to 0..255.  The one-pixel border is copied
+ *                    unchanged; an image with h < 3 or w < 3 is all border.
+ *   hp_aug_rgb_blur  Pillow's GaussianBlur of integer radius k as three box passes along the rows, then three along the columns,
+ *                    EVERY pass rounded to uint8.  The HOST computes per image, in float32: sigma2 = k k / 3,
+ *                    L = sqrt(12 sigma2 + 1), l = floor((L - 1) / 2), a = (2 l + 1)(l (l + 1) - 3 sigma2) / (6 (sigma2 - (l + 1)^2)),
+ *                    r_f = l + a (0.25000003, 1.375, 2.4166667 for k = 1, 2, 3); d_radius = r = (int) r_f,
+ *                    d_ww = (uint32)(2^24 / (2 r_f + 1)) in float32, d_fw = (2^24 - (2 r + 1) ww) / 2.  One pass along a line is
+ *                      out[x] = (ww sum_{i = -r..r} in[clamp(x + i)] + fw (in[clamp(x - r - 1)] + in[clamp(x + r + 1)]) + 2^23) >> 24
+ *                    in 32-bit unsigned integers, indices clamped to the line.  A line of at most 1024 pixels runs its three
+ *                    passes in the LDS (rows: one workgroup per line; columns: one per 8 columns); a longer one, or every one
+ *                    with force_general != 0, takes one launch per pass through the workspace.  Both paths give the same bytes.
+ *   hp_aug_replace_background   out = background where segmentation == 0, else rgb.  d_background is already at frame size.
+ *
+ * Depth: the reference's definitions restated; it calls OpenCV (resize, ellipse, blur), which is not a dependency, so parity with
+ * OpenCV is UNPINNED and what follows is the whole contract.  The reference's random streams (the global `random` / `np.random`
+ * state) are not reproduced either.
+ *   Random numbers   Philox4x32-10 as for hp_mesh_sample_surface, key (seed & 0xffffffff, seed >> 32), counter
+ *                    (index, b, stream, 0): index = the pixel's row-major index in its image, or the cell's in its grid; b = the
+ *                    image's index in the call; stream = HP_AUG_STREAM_NOISE (1), _GRID (2) or _MISSING (3).  A normal deviate is
+ *                    Box-Muller in float32 on words r0, r1: u1 = ((r0 >> 8) + 1) 2^-24 in (0, 1], u2 = (r1 >> 8) 2^-24,
+ *                    n = sqrt(-2 ln u1) cos(6.2831855f u2).
+ *   hp_aug_depth_noise, correlated == 0    where depth > 0: depth = clip(depth + std n, 0, FLT_MAX).  depth > 0 is false for NaN:
+ *                    NaN stays, and so do 0 and negative values (the reference's np.clip would raise a negative one to 0).
+ *   hp_aug_depth_noise, correlated != 0    a grid of d_grid_h[b] x d_grid_w[b] cells (the host's int(h / f), int(w / f)), cell c =
+ *                    std n(c), is upsampled to h x w bicubically as OpenCV documents INTER_CUBIC: for output x,
+ *                    fx = (x + 0.5)(gw / w) - 0.5, sx = floor(fx), t = fx - sx, taps sx - 1 .. sx + 2 clamped to the grid with
+ *                      w0 = ((A (t + 1) - 5 A)(t + 1) + 8 A)(t + 1) - 4 A,  w1 = ((A + 2) t - (A + 3)) t t + 1,
+ *                      w2 = ((A + 2)(1 - t) - (A + 3))(1 - t)(1 - t) + 1,   w3 = 1 - w0 - w1 - w2,   A = -0.75,
+ *                    the same along y; value = sum_j wy_j (sum_i wx_i g[y_j][x_i]), both sums from tap 0 onto 0, in float32.
+ *                    It is added where depth > 0 and the sum clipped as above.  A grid with a side <= 0 (or more cells than
+ *                    pixels) leaves the image unchanged.
+ *   hp_aug_depth_missing   of the n_valid pixels with depth > 0 exactly m = (int)(d_fraction[b] * n_valid) (double; at most n_valid)
+ *                    become 0: the m with the smallest (r0, pixel index) pairs, r0 from stream _MISSING.  One workgroup per
+ *                    image: the words go to the workspace, then a radix select, 8 bits a pass with an integer histogram in the
+ *                    LDS, finds the m-th smallest 64-bit key (r0 << 32 | pixel).  No sort, no host round trip.  n_valid == 0 or
+ *                    m == 0 leaves the image unchanged.
+ *   hp_aug_depth_ellipses  d_table [B][max_ellipses][5] float32 = (u, rx, ry, angle_deg, value), d_count [B] int32 (clamped to
+ *                    0 .. max_ellipses).  The centre (cx, cy) of ellipse e is the floor(u n_valid)-th (double; clamped to
+ *                    n_valid - 1) valid pixel in row-major order, found on the device by a prefix count over groups of 64 pixels.
+ *                    rx, ry are the radii the host has rounded to integers.  With dx = x - cx, dy = y - cy,
+ *                    th = angle_deg * 0.017453292f:  x' = dx cos th + dy sin th,  y' = dy cos th - dx sin th, a pixel is inside when
+ *                    (x' / max(rx, 0.5))^2 + (y' / max(ry, 0.5))^2 <= 1  in float32.  noise == 0: inside pixels become 0.
+ *                    noise != 0: where depth > 0, depth += the value of the LAST ellipse in table order that covers the pixel
+ *                    (no clip, as in the reference).  n_valid == 0 leaves the image unchanged -- the reference raises there.
+ *                    OpenCV fills a polygon approximation of the ellipse: boundary pixels may differ (unpinned).
+ *   hp_aug_depth_blur      the k x k normalised box filter, k = d_ksize[b], border reflect-101, anchor k / 2 (integer division:
+ *                    k = 4 covers x - 2 .. x + 1): the k k values are added in float32 onto 0, rows from the top, each row from
+ *                    the left, and the sum divided by (float)(k k).  Zeros take part, as in the reference.  k_max is the HOST's
+ *                    bound on d_ksize: k_max > h or k_max > w is HP_ERR_ARG (reflect-101 is not defined) and launches nothing; an
+ *                    image whose k is outside 1 .. k_max is left unchanged.
+ *   hp_aug_depth_mask      d_segmentation == NULL: depth = 0 (DepthDropout); else depth = 0 where segmentation == 0.
+ * ---------------------------------------------------------------------------------- */
+#define HP_AUG_OP_BRIGHTNESS 0
+#define HP_AUG_OP_COLOR 1
+#define HP_AUG_OP_CONTRAST 2
+#define HP_AUG_OP_SHARPNESS 3
+#define HP_AUG_STREAM_NOISE 1
+#define HP_AUG_STREAM_GRID 2
+#define HP_AUG_STREAM_MISSING 3
+int64_t hp_aug_workspace_bytes(int B, int h, int w, int max_ellipses);
+int hp_aug_rgb_enhance(int B, int h, int w, const uint8_t* d_rgb, const int32_t* d_op, const float* d_factor, const uint8_t* d_apply,
+                       uint8_t* d_out, void* d_workspace, int64_t workspace_bytes, void* stream);
+int hp_aug_rgb_blur(int B, int h, int w, const uint8_t* d_rgb, const int32_t* d_radius, const uint32_t* d_ww, const uint32_t* d_fw,
+                    const uint8_t* d_apply, uint8_t* d_out, int force_general, void* d_workspace, int64_t workspace_bytes,
+                    void* stream);
+int hp_aug_replace_background(int B, int h, int w, const uint8_t* d_rgb, const int32_t* d_segmentation, const uint8_t* d_background,
+                              const uint8_t* d_apply, uint8_t* d_out, void* stream);
+int hp_aug_depth_noise(int B, int h, int w, const float* d_depth, const float* d_std, int correlated, const int32_t* d_grid_h,
+                       const int32_t* d_grid_w, const uint8_t* d_apply, uint64_t seed, float* d_out, void* d_workspace,
+                       int64_t workspace_bytes, void* stream);
+int hp_aug_depth_missing(int B, int h, int w, const float* d_depth, const double* d_fraction, const uint8_t* d_apply, uint64_t seed,
+                         float* d_out, void* d_workspace, int64_t workspace_bytes, void* stream);
+int hp_aug_depth_ellipses(int B, int h, int w, const float* d_depth, const float* d_table, const int32_t* d_count, int max_ellipses,
+                          int noise, const uint8_t* d_apply, float* d_out, void* d_workspace, int64_t workspace_bytes, void* stream);
+int hp_aug_depth_blur(int B, int h, int w, const float* d_depth, const int32_t* d_ksize, int k_max, const uint8_t* d_apply,
+                      float* d_out, void* stream);
+int hp_aug_depth_mask(int B, int h, int w, const float* d_depth, const int32_t* d_segmentation, const uint8_t* d_apply, float* d_out,
+                      void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

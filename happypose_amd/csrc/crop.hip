@@ -13,9 +13,13 @@
 // (wy_lo[iy] I[y_lo] + wy_hi[iy] I[y_hi]) x (wx_lo[ix] I[x_lo] + wx_hi[ix] I[x_hi]), so the
 // pixel is sum_r sum_c Wy[r] Wx[c] I[r][c] over the DISTINCT rows/columns the samples touch.
 // Crops up-sample or mildly down-sample the frame (bin <= ~2.5 px), so that is 2-5 rows x 2-5
-// columns = 4-25 loads per channel instead of 64.  Pixels whose samples span more than 5
-// rows or columns (bin > 2.67 px: crop boxes wider than ~850 px) take the literal 16-sample
-// path.  The factorisation only re-associates the fp32 sum (<= 1e-6 relative).
+// columns = 4-25 loads per channel instead of 64.  A tile with a pixel whose samples span more
+// than kSpan = 5 rows or columns takes the literal 16-sample path.  The g samples of a pixel
+// lie (g-1)/g bins apart end to end and touch at most floor((g-1)/g bin) + 3 indices, so a
+// span of 6 needs (g-1)/g bin > 3: bin > 4 source pixels at the default g = 4 (a box wider
+// than 1280 px at 320 output columns), > 4.5 at g = 3, > 6 at g = 2, never at g = 1
+// (tests/crop_ref.py axis_spans; both paths and mixed tiles: tests/test_gpu_crop_paths.py).
+// The factorisation only re-associates the fp32 sum (<= 1e-6 relative).
 #include <cstdlib>
 
 #include "common.h"

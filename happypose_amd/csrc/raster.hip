@@ -1303,7 +1303,8 @@ __global__ __launch_bounds__(band_threads(NS, WIDE), (NS == 1 && !HALF && !ANISO
         store_run(o + c0, rend, nrend);
       }
       if (ncrop > 0 && !separable) {
-        // strongly down-sampling crop (a bin spans more than kSpan source pixels: boxes wider than ~850 px): the literal
+        // strongly down-sampling crop (some pixel of the band touches more than kSpan source rows or columns: bin > 4 source
+        // pixels at sampling ratio 4, see crop.hip; tests/test_gpu_crop_paths.py runs it): the literal
         // sampling_ratio^2-sample evaluation, one channel at a time in a rolled loop (rare; keeps it out of the
         // register budget of the common path), stored after the record so that it lands on top of the zeros above
 #pragma unroll 1

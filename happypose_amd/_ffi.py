@@ -208,6 +208,12 @@ _PROTOS = {
                                         C.c_int64, C.c_void_p]),
     "hp_aug_depth_blur": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, C.c_int, c_u8p, c_f32p, C.c_void_p]),
     "hp_aug_depth_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, c_u8p, c_f32p, C.c_void_p]),
+    "hp_resize_workspace_bytes": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "hp_resize_rgb": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, c_u8p, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int,
+                                c_i32p, c_i32p, C.c_int, c_u8p, c_u8p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_resize_nearest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_i32p, c_i32p, c_i32p, c_u8p,
+                                    C.c_void_p, C.c_void_p]),
+    "hp_seg_boxes": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -8,9 +8,11 @@ the kernels.  ``__call__(batch, rng)`` does both.  ``SceneObservationAugmentatio
 ``apply`` flags: an image is transformed with probability ``p``, and only if every enclosing augmentation applied as well.
 
 The RGB transforms equal Pillow byte for byte.  The depth transforms restate the reference's OpenCV calls (parity unpinned).
-The reference's random STREAMS are not reproduced: they come from the global ``random`` / ``np.random`` state.  Out of scope:
-``CropResizeToAspectTransform``, loading VOC and resizing a background image -- ``ObservationBatch.background`` is already at
-frame size.
+The reference's random STREAMS are not reproduced: they come from the global ``random`` / ``np.random`` state.
+
+``CropResizeToAspectTransform`` is the one transform that changes a frame's geometry (``csrc/resize.hip``): it equals Pillow's
+``crop`` and ``resize`` byte for byte, rewrites ``K`` and recomputes the modal boxes from the resized id map.  Out of scope:
+loading VOC -- the background frames come with the batch (``ReplaceBackgroundTransform(resize_background=True)`` resizes them).
 """
 
 from __future__ import annotations
@@ -27,12 +29,20 @@ from . import ops
 @dataclasses.dataclass
 class ObservationBatch:
     """``rgb [B, H, W, 3]`` uint8, ``depth [B, H, W]`` float32 (metres, 0 = invalid), ``segmentation [B, H, W]`` int32 (0 =
-    background: ``SceneRenderer``'s ``ids + 1``), ``background [B, H, W, 3]`` uint8; all dense, on the device."""
+    background: ``SceneRenderer``'s ``ids + 1``), ``background [B, H, W, 3]`` uint8 (``[B, H', W', 3]`` with
+    ``ReplaceBackgroundTransform(resize_background=True)``); all dense, on the device.  Optional, for
+    ``CropResizeToAspectTransform``: ``K [B, 3, 3]`` (any device) and ``object_ids``, one list of unique ids per image -- the
+    transform then fills ``boxes_modal [B, max_ids, 4]`` int32 ``(x1, y1, x2, y2)``, inclusive, and ``visible [B, max_ids]``
+    bool, slot ``k`` of image ``b`` for ``object_ids[b][k]`` (a slot that is not visible has an unspecified box)."""
 
     rgb: Optional[torch.Tensor] = None
     depth: Optional[torch.Tensor] = None
     segmentation: Optional[torch.Tensor] = None
     background: Optional[torch.Tensor] = None
+    K: Optional[torch.Tensor] = None
+    object_ids: Optional[Sequence[Sequence[int]]] = None
+    boxes_modal: Optional[torch.Tensor] = None
+    visible: Optional[torch.Tensor] = None
 
     @property
     def batch_size(self) -> int:
@@ -155,12 +165,95 @@ class PillowBlur(SceneObservationTransform):
 
 
 class ReplaceBackgroundTransform(SceneObservationTransform):
-    """``rgb[segmentation == 0] = background[segmentation == 0]`` with ``batch.background``, already at frame size."""
+    """``rgb[segmentation == 0] = background[segmentation == 0]`` with ``batch.background``, already at frame size.  With
+    ``resize_background=True`` a background of another size is first resized as the reference's ``PIL.Image.resize((w, h))``
+    does it: with Pillow's default filter, bicubic."""
+
+    def __init__(self, resize_background: bool = False):
+        self.resize_background = resize_background
 
     def apply(self, batch, params, apply=None):
         assert batch.rgb is not None and batch.segmentation is not None and batch.background is not None
         flags = _all(batch.batch_size) if apply is None else apply
-        return dataclasses.replace(batch, rgb=ops.aug_replace_background(batch.rgb, batch.segmentation, batch.background, flags))
+        background = batch.background
+        if self.resize_background and background.shape[1:3] != batch.rgb.shape[1:3]:
+            background = ops.resize_rgb(background, batch.rgb.shape[1:3], "bicubic")
+        return dataclasses.replace(batch, rgb=ops.aug_replace_background(batch.rgb, batch.segmentation, background, flags))
+
+
+# ---- geometry -----------------------------------------------------------------------------------------------------------------------
+def k_crop_resize(K: np.ndarray, box: Sequence[float], crop_resize: Tuple[float, float]) -> np.ndarray:
+    """The reference's ``get_K_crop_resize`` (lib3d/camera_geometry.py; ``csrc/crop_math.h`` has the same closed form) for
+    ``K [B, 3, 3]`` and ONE float box ``(x1, y1, x2, y2)``, in float32: the focal lengths scale by final / crop size, the
+    principal point moves with the crop's centre and is rescaled about the pixel centres."""
+    f32 = np.float32
+    K = np.asarray(K, f32)
+    x1, y1, x2, y2 = (f32(v) for v in box)
+    final_w, final_h = f32(max(crop_resize)), f32(min(crop_resize))
+    crop_w, crop_h = x2 - x1, y2 - y1
+    centre_x, centre_y = (crop_w - f32(1)) / f32(2), (crop_h - f32(1)) / f32(2)
+    cx = K[:, 0, 2] + centre_x - (x1 + x2) / f32(2)
+    cy = K[:, 1, 2] + centre_y - (y1 + y2) / f32(2)
+    scale_x, scale_y = final_w / crop_w, final_h / crop_h
+    new_K = K.copy()
+    new_K[:, 0, 0] = scale_x * K[:, 0, 0]
+    new_K[:, 1, 1] = scale_y * K[:, 1, 1]
+    new_K[:, 0, 2] = (final_w - f32(1)) / f32(2) + scale_x * (cx - centre_x)
+    new_K[:, 1, 2] = (final_h - f32(1)) / f32(2) + scale_y * (cy - centre_y)
+    return new_K
+
+
+class CropResizeToAspectTransform(SceneObservationTransform):
+    """The first transform of the reference's chains: frames whose size is not ``resize = (h, w)`` are cropped about their
+    centre to its aspect (``PIL.Image.crop`` of the reference's float box: every edge rounded, halves to the even integer; a
+    frame that is too wide is padded with zeros, as there) and resized -- RGB with Pillow's BILINEAR, segmentation and depth with
+    NEAREST.  ``K`` goes through ``get_K_crop_resize`` twice, with the float box and crop sizes the reference passes (on the
+    host: it is 9 numbers per image); ``boxes_modal`` / ``visible`` are recomputed from the resized segmentation for
+    ``batch.object_ids``.  ``bbox_amodal`` and ``visib_fract``, which the reference drops, are not part of the batch.  A batch
+    that already has the size comes back as it is.  The transform changes the frames' size, so it cannot apply to a part of a
+    batch: ``apply`` flags that are not all set raise ValueError."""
+
+    def __init__(self, resize: Tuple[int, int] = (480, 640)):
+        assert resize[1] >= resize[0]
+        self.resize = (int(resize[0]), int(resize[1]))
+        self.aspect = max(resize) / min(resize)
+
+    def crop_box(self, h: int, w: int) -> Optional[Tuple[float, float, float, float]]:
+        """The float box ``(x1, y1, x2, y2)`` of the centre crop; None when ``w / h`` is close to the aspect."""
+        if np.isclose(w / h, self.aspect):
+            return None
+        crop_h = w * 1 / self.aspect
+        crop_h, crop_w = min(crop_h, w), max(crop_h, w)
+        x0, y0 = w / 2, h / 2
+        return (x0 - crop_w / 2, y0 - crop_h / 2, x0 + crop_w / 2, y0 + crop_h / 2)
+
+    def apply(self, batch, params, apply=None):
+        assert batch.rgb is not None
+        assert batch.segmentation is not None
+        if apply is not None and not np.asarray(apply, bool).all():
+            raise ValueError("CropResizeToAspectTransform changes the frame size: it applies to every image of a batch or to none")
+        h, w = int(batch.rgb.shape[1]), int(batch.rgb.shape[2])
+        if (h, w) == self.resize:
+            return batch
+        K = None if batch.K is None else np.asarray(batch.K.detach().cpu(), np.float32).reshape(-1, 3, 3)
+        box, rect = self.crop_box(h, w), None
+        if box is not None:
+            rect = tuple(int(round(v)) for v in box)  # PIL.Image.crop
+            if K is not None:
+                K = k_crop_resize(K, box, (box[3] - box[1], box[2] - box[0]))
+            h, w = rect[3] - rect[1], rect[2] - rect[0]
+        out_hw = (min(self.resize), max(self.resize))
+        rgb = ops.resize_rgb(batch.rgb, out_hw, "bilinear", crop=rect)
+        segmentation = ops.resize_nearest(batch.segmentation, out_hw, crop=rect)
+        depth = None if batch.depth is None else ops.resize_nearest(batch.depth, out_hw, crop=rect)
+        new = dataclasses.replace(batch, rgb=rgb, segmentation=segmentation, depth=depth)
+        if K is not None:
+            K = k_crop_resize(K, (0, 0, w, h), out_hw)
+            new.K = torch.from_numpy(K).to(device=batch.K.device, dtype=batch.K.dtype).reshape(batch.K.shape)
+        if batch.object_ids is not None:
+            boxes, n_px = ops.seg_boxes(segmentation, batch.object_ids)
+            new.boxes_modal, new.visible = boxes, n_px > 0
+        return new
 
 
 # ---- depth --------------------------------------------------------------------------------------------------------------------------

@@ -8,6 +8,7 @@ happens in the HIP library.  Each wrapper validates what the reference asserts
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -1836,3 +1837,236 @@ def aug_depth_mask(depth: torch.Tensor, segmentation: Optional[torch.Tensor] = N
             check(lib().hp_aug_depth_mask(B, h, w, ptr(depth), ptr(seg), ptr(_p0), ptr(out), stream_ptr(dev)),
                   "hp_aug_depth_mask")
     return out
+
+
+# ------------------------------------------------------------------------------------------------- frame geometry (resize.hip)
+RESIZE_FILTERS = {"bilinear": 1.0, "bicubic": 2.0}  # the filter's support
+RESIZE_PRECISION_BITS = 22
+RESIZE_TILE = 256        # output pixels per workgroup of the pass along x (csrc/resize.hip: kTile)
+RESIZE_MAX_BAND = 12288  # csrc/resize.hip: kMaxBand
+SEG_BOXES_MAX_IDS = 256
+
+
+def _resize_filter(name: str, x: np.ndarray) -> np.ndarray:
+    x = np.abs(x)
+    if name == "bilinear":
+        return np.where(x < 1.0, 1.0 - x, 0.0)
+    a = -0.5
+    return np.where(x < 1.0, ((a + 2.0) * x - (a + 3.0)) * x * x + 1, np.where(x < 2.0, (((x - 5) * x + 8) * x - 4) * a, 0.0))
+
+
+@functools.lru_cache(maxsize=256)
+def _resize_axis(size: int, b0: int, b1: int, out: int, filt: str) -> Tuple[np.ndarray, np.ndarray]:
+    """Pillow's coefficients of one axis in float64: ``bounds [out, 2]`` = (first source index, count) and the fixed-point
+    ``weights [out, ksize]`` (0 beyond the count).  The header writes the formulas out."""
+    scale = (b1 - b0) / out
+    fscale = max(scale, 1.0)
+    support = RESIZE_FILTERS[filt] * fscale
+    ksize = int(np.ceil(support)) * 2 + 1
+    centre = b0 + (np.arange(out, dtype=np.float64) + 0.5) * scale
+    lo = np.maximum((centre - support + 0.5).astype(np.int64), 0)  # the cast truncates, as C's
+    hi = np.minimum((centre + support + 0.5).astype(np.int64), size)
+    n = np.maximum(hi - lo, 0)
+    k = np.arange(ksize)
+    w = _resize_filter(filt, (k[None, :] + lo[:, None] - centre[:, None] + 0.5) * (1.0 / fscale))
+    w = np.where(k[None, :] < n[:, None], w, 0.0)
+    total = np.zeros(out)
+    for j in range(ksize):  # the window's sum in Pillow's order
+        total = total + w[:, j]
+    w = np.where(total[:, None] != 0.0, w / np.where(total == 0.0, 1.0, total)[:, None], w)
+    q = np.trunc(np.where(w < 0, -0.5, 0.5) + w * float(1 << RESIZE_PRECISION_BITS)).astype(np.int32)
+    return np.stack([lo, n], axis=1).astype(np.int32), q
+
+
+@functools.lru_cache(maxsize=256)
+def _nearest_axis(size: int, b0: int, b1: int, out: int) -> np.ndarray:
+    """Pillow's NEAREST source index per output index: the running double sum, -1 outside ``0 .. size - 1``."""
+    step = (b1 - b0) / out
+    t = np.add.accumulate(np.concatenate([[b0 + step * 0.5], np.full(out - 1, step)]))  # sequential: t[i + 1] = t[i] + step
+    j = np.where(t < 0.0, -1, np.minimum(t, 2.0 ** 31).astype(np.int64))
+    return np.where((j >= 0) & (j < size), j, -1).astype(np.int32)
+
+
+def _resize_geometry(in_size, box, crop) -> Tuple[int, int, int, int, int, int, int, int, int, int]:
+    h, w = int(in_size[0]), int(in_size[1])
+    cx0, cy0, cx1, cy1 = (0, 0, w, h) if crop is None else (int(v) for v in crop)
+    if cx1 <= cx0 or cy1 <= cy0:
+        raise ValueError(f"resize: empty crop rectangle {(cx0, cy0, cx1, cy1)}")
+    vw, vh = cx1 - cx0, cy1 - cy0
+    x0, y0, x1, y1 = (0, 0, vw, vh) if box is None else (int(v) for v in box)
+    if not (0 <= x0 < x1 <= vw and 0 <= y0 < y1 <= vh):  # Pillow: "box can't exceed original image size / can't be empty"
+        raise ValueError(f"resize: box {(x0, y0, x1, y1)} must be non-empty and inside the {vh} x {vw} image")
+    return h, w, cx0, cy0, vw, vh, x0, y0, x1, y1
+
+
+def resize_tables(in_size, out_size, box=None, filter: str = "bilinear", crop=None) -> Dict[str, object]:
+    """The host half of ``hp_resize_rgb`` for ONE geometry: frames of ``in_size = (h, w)`` are cropped to the integer rectangle
+    ``crop = (x0, y0, x1, y1)`` as ``PIL.Image.crop`` does (default: the frame; outside the frame is 0), then resized to
+    ``out_size = (h, w)`` with ``box`` (integer pixels of the cropped image, default: all of it) and ``filter``.  Returns
+    ``xbounds [ow, 2]``, ``xweights [ow, ksize_x]``, ``ybounds``, ``yweights`` (int32, bounds in SOURCE pixels), ``skip_x`` /
+    ``skip_y`` (Pillow would skip the pass AND the pass is the identity in source pixels) and ``band_x``."""
+    if filter not in RESIZE_FILTERS:
+        raise ValueError(f"resize: filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
+    h, w, cx0, cy0, vw, vh, x0, y0, x1, y1 = _resize_geometry(in_size, box, crop)
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if oh < 1 or ow < 1:
+        raise ValueError("resize: empty output")
+    xb, xw = _resize_axis(vw, x0, x1, ow, filter)
+    yb, yw = _resize_axis(vh, y0, y1, oh, filter)
+    xb, yb = xb + np.array([cx0, 0], np.int32), yb + np.array([cy0, 0], np.int32)
+    first = np.arange(0, ow, RESIZE_TILE)
+    last = np.minimum(first + RESIZE_TILE, ow) - 1
+    lo = np.clip(xb[first, 0], 0, w)
+    band = int(np.max(np.minimum(np.maximum(xb[last, 0] + xb[last, 1], lo), w) - lo))
+    return {"xbounds": xb, "xweights": xw, "ybounds": yb, "yweights": yw, "band_x": max(band, 1),
+            "skip_x": ow == vw == w and (cx0, x0, x1) == (0, 0, vw), "skip_y": oh == vh == h and (cy0, y0, y1) == (0, 0, vh)}
+
+
+def _resize_rects(v, B: int, what: str) -> List[Optional[Tuple[int, ...]]]:
+    """``None``, one rectangle or one per image -> ``B`` tuples of 4 integers (or ``None``)."""
+    if v is None:
+        return [None] * B
+    a = np.asarray(v.detach().cpu() if isinstance(v, torch.Tensor) else v)
+    if a.shape not in ((4,), (B, 4)) or not np.issubdtype(a.dtype, np.number) or (a != np.round(a)).any():
+        raise ValueError(f"{what}: 4 integers (x0, y0, x1, y1), or [B, 4]")
+    a = np.broadcast_to(a.astype(np.int64), (B, 4))
+    return [tuple(int(x) for x in r) for r in a]
+
+
+def _resize_sets(B: int, box, crop, what: str):
+    """The distinct (box, crop) pairs of a batch and ``table_of [B]``."""
+    pairs = list(zip(_resize_rects(box, B, f"{what}: box"), _resize_rects(crop, B, f"{what}: crop")))
+    keys: Dict[tuple, int] = {}
+    table_of = np.array([keys.setdefault(p, len(keys)) for p in pairs], np.int32)
+    return list(keys), table_of
+
+
+def _resize_out(x: torch.Tensor, out_size, out: Optional[torch.Tensor], partial: bool, what: str) -> torch.Tensor:
+    oh, ow = int(out_size[0]), int(out_size[1])
+    if oh < 1 or ow < 1:
+        raise ValueError(f"{what}: empty output")
+    shape = (x.shape[0], oh, ow) + tuple(x.shape[3:])
+    if out is None:  # an image that is not applied keeps what out held: zeros here
+        return (torch.zeros if partial else torch.empty)(shape, dtype=x.dtype, device=x.device)
+    if tuple(out.shape) != shape or out.dtype != x.dtype or out.device != x.device or not out.is_contiguous():
+        raise ValueError(f"{what}: out must be {shape} {x.dtype} on the input's device")
+    if out.data_ptr() == x.data_ptr():
+        raise ValueError(f"{what}: out must not alias the input")
+    return out
+
+
+def _pad_stack(tables: List[np.ndarray]) -> np.ndarray:
+    k = max(t.shape[1] for t in tables)
+    return np.stack([np.pad(t, ((0, 0), (0, k - t.shape[1]))) for t in tables])
+
+
+def resize_rgb(rgb: torch.Tensor, out_size, filter: str = "bilinear", box=None, crop=None, apply=None,
+               out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_resize_rgb``: ``PIL.Image.resize(out_size[::-1], filter, box)`` of every frame of ``rgb [B, H, W, 3]`` uint8, after
+    ``PIL.Image.crop(crop)`` when ``crop`` is given; byte for byte.  ``box`` / ``crop``: 4 integers ``(x0, y0, x1, y1)`` or one row
+    per image (``[B, 4]``); images with the same pair share one table set.  ``apply [B]`` bool (default all): an image that is
+    not applied keeps what ``out`` held (zeros without ``out``).  Not in place."""
+    rgb = _aug_frames(rgb, "resize_rgb: rgb", torch.uint8, True)
+    B, h, w, dev = rgb.shape[0], rgb.shape[1], rgb.shape[2], rgb.device
+    if filter not in RESIZE_FILTERS:
+        raise ValueError(f"resize_rgb: filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
+    out = _resize_out(rgb, out_size, out, apply is not None, "resize_rgb")
+    if B == 0:
+        return out
+    oh, ow = out.shape[1], out.shape[2]
+    sets, table_of = _resize_sets(B, box, crop, "resize_rgb")
+    tabs = [resize_tables((h, w), (oh, ow), bx, filter, cr) for bx, cr in sets]
+    pass_x, pass_y = not all(t["skip_x"] for t in tabs), not all(t["skip_y"] for t in tabs)
+    band = max(t["band_x"] for t in tabs)
+    if pass_x and band > RESIZE_MAX_BAND:
+        raise ValueError(f"resize_rgb: {RESIZE_TILE} output pixels cover {band} source pixels, more than the {RESIZE_MAX_BAND} one band holds")
+    xb = xw = yb = yw = ws = None
+    ksx = ksy = nbytes = 0
+    if pass_x:
+        xb, xw = torch.from_numpy(np.stack([t["xbounds"] for t in tabs])).to(dev), torch.from_numpy(_pad_stack([t["xweights"] for t in tabs])).to(dev)
+        ksx = xw.shape[2]
+    if pass_y:
+        yb, yw = torch.from_numpy(np.stack([t["ybounds"] for t in tabs])).to(dev), torch.from_numpy(_pad_stack([t["yweights"] for t in tabs])).to(dev)
+        ksy = yw.shape[2]
+    if pass_x and pass_y:
+        nbytes = int(lib().hp_resize_workspace_bytes(B, h, ow))
+        if nbytes < 0:
+            raise ValueError("resize_rgb: at most 65535 frames of at most 2^28 pixels")
+        ws = torch.empty(max(nbytes // 8, 1), dtype=torch.int64, device=dev)
+    _p0 = torch.from_numpy(table_of).to(dev)
+    _p1 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_resize_rgb(B, h, w, oh, ow, ptr(rgb), len(tabs), ptr(_p0), ptr(xb), ptr(xw), ksx, band if pass_x else 0, ptr(yb), ptr(yw),
+                                  ksy, ptr(_p1), ptr(out), ptr(ws), nbytes, stream_ptr(dev)), "hp_resize_rgb")
+    return out
+
+
+def resize_nearest(x: torch.Tensor, out_size, box=None, crop=None, apply=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_resize_nearest``: ``PIL.Image.resize(out_size[::-1], NEAREST, box)`` of ``x [B, H, W]`` int32 (mode I) or float32 (mode
+    F), after ``PIL.Image.crop(crop)`` when given: a copy of bits.  ``box``, ``crop``, ``apply``, ``out`` as for ``resize_rgb``."""
+    if not isinstance(x, torch.Tensor) or not x.is_cuda:
+        raise ValueError("resize_nearest: a tensor on the device is required (no CPU implementation)")
+    if x.dtype not in (torch.int32, torch.float32):
+        raise ValueError(f"resize_nearest: int32 or float32 frames expected, got {x.dtype}")
+    x = _aug_frames(x, "resize_nearest: x", x.dtype, False)
+    B, h, w, dev = x.shape[0], x.shape[1], x.shape[2], x.device
+    out = _resize_out(x, out_size, out, apply is not None, "resize_nearest")
+    if B == 0:
+        return out
+    oh, ow = out.shape[1], out.shape[2]
+    sets, table_of = _resize_sets(B, box, crop, "resize_nearest")
+    xi, yi = [], []
+    for bx, cr in sets:
+        _, _, cx0, cy0, vw, vh, x0, y0, x1, y1 = _resize_geometry((h, w), bx, cr)
+        jx, jy = _nearest_axis(vw, x0, x1, ow), _nearest_axis(vh, y0, y1, oh)
+        xi.append(np.where(jx >= 0, jx + cx0, -1))
+        yi.append(np.where(jy >= 0, jy + cy0, -1))
+    _p0 = torch.from_numpy(table_of).to(dev)
+    _p1 = torch.from_numpy(np.stack(xi).astype(np.int32)).to(dev)
+    _p2 = torch.from_numpy(np.stack(yi).astype(np.int32)).to(dev)
+    _p3 = _aug_apply(apply, B, dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_resize_nearest(B, h, w, oh, ow, ptr(x), len(sets), ptr(_p0), ptr(_p1), ptr(_p2), ptr(_p3), ptr(out), stream_ptr(dev)),
+              "hp_resize_nearest")
+    return out
+
+
+def seg_boxes_table(ids, B: int) -> Tuple[np.ndarray, np.ndarray]:
+    """Per-image id lists (or an array ``[B, max_ids]``) -> ``(table [B, max_ids] int32, count [B] int32)``, padded with 0."""
+    rows = [np.asarray(r.detach().cpu() if isinstance(r, torch.Tensor) else r, np.int64).reshape(-1) for r in ids]
+    if len(rows) != B:
+        raise ValueError(f"seg_boxes: one id list per image ({B}), got {len(rows)}")
+    count = np.array([r.size for r in rows], np.int32)
+    table = np.zeros((B, max(int(count.max()) if B else 0, 1)), np.int32)
+    for b, r in enumerate(rows):
+        if r.size and (r.min() < -2 ** 31 or r.max() >= 2 ** 31):
+            raise ValueError("seg_boxes: ids must fit int32")
+        table[b, :r.size] = r
+    return table, count
+
+
+def seg_boxes(segmentation: torch.Tensor, ids, count=None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``hp_seg_boxes``: ``(boxes [B, max_ids, 4] int32 (x1, y1, x2, y2), inclusive; n_px [B, max_ids] int32)`` of the ids of
+    every image in ``segmentation [B, H, W]`` int32.  ``ids``: per-image lists, or an int32 device tensor ``[B, max_ids]`` with
+    ``count [B]`` (default: all ``max_ids``).  A slot with ``n_px == 0`` (absent id, padding) has an unspecified box."""
+    seg = _aug_frames(segmentation, "seg_boxes: segmentation", torch.int32, False)
+    B, h, w, dev = seg.shape[0], seg.shape[1], seg.shape[2], seg.device
+    if isinstance(ids, torch.Tensor) and ids.is_cuda:
+        if ids.dtype != torch.int32 or ids.dim() != 2 or ids.shape[0] != B or ids.shape[1] < 1 or not ids.is_contiguous() or ids.device != dev:
+            raise ValueError("seg_boxes: ids must be a dense [B, max_ids] int32 tensor on the segmentation's device")
+        table = ids
+        cnt = _aug_param(ids.shape[1] if count is None else count, B, torch.int32, dev, "count")
+    else:
+        if count is not None:
+            raise ValueError("seg_boxes: count goes with a device tensor of ids; lists carry their own lengths")
+        t, c = seg_boxes_table(ids, B)
+        table, cnt = torch.from_numpy(t).to(dev), torch.from_numpy(c).to(dev)
+    max_ids = int(table.shape[1])
+    if max_ids > SEG_BOXES_MAX_IDS:
+        raise ValueError(f"seg_boxes: at most {SEG_BOXES_MAX_IDS} ids per image, got {max_ids}")
+    boxes = torch.empty((B, max_ids, 4), dtype=torch.int32, device=dev)
+    n_px = torch.empty((B, max_ids), dtype=torch.int32, device=dev)
+    if B:
+        with torch.cuda.device(dev):
+            check(lib().hp_seg_boxes(B, h, w, ptr(seg), ptr(table), ptr(cnt), max_ids, ptr(boxes), ptr(n_px), stream_ptr(dev)), "hp_seg_boxes")
+    return boxes, n_px

@@ -1152,6 +1152,63 @@ int hp_aug_depth_blur(int B, int h, int w, const float* d_depth, const int32_t* 
 int hp_aug_depth_mask(int B, int h, int w, const float* d_depth, const int32_t* d_segmentation, const uint8_t* d_apply, float* d_out,
                       void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Frame geometry: Pillow-exact resize of a batch of frames that already lives on the device, and modal boxes from an id map --
+ * what the reference's CropResizeToAspectTransform and ReplaceBackgroundTransform do with PIL.Image.crop / resize and
+ * make_detections_from_segmentation.  csrc/resize.hip; the user-facing layer is happypose_amd/augmentations.py.
+ *
+ * All images of a call share the input size, the output size and the filter.  The geometry of image b -- its crop rectangle and its
+ * source box -- is in TABLE SET d_table_of[b] (0 .. n_tables - 1; another value leaves the image's output untouched): the host
+ * computes the tables (happypose_amd.ops.resize_tables, float64), so the box may differ per image exactly when the images name
+ * different table sets, and images with the same geometry share one.  There is therefore no box argument: the tables hold SOURCE
+ * pixel indices.  A tap or an index outside the frame reads 0 -- that is PIL.Image.crop's padding when a crop rectangle leaves the
+ * frame -- and the kernels clamp every count to the table's width, so no table content can make them touch memory outside the
+ * buffers they were given.  d_apply [B] uint8: the OUTPUT of an image with d_apply[b] == 0 is not written (it keeps what d_out
+ * held).  d_out must not alias d_in.  B == 0 returns HP_OK and launches nothing; a null pointer, a size <= 0, B > 65535, more than
+ * 2^28 pixels per image or out_h > 65535 is HP_ERR_ARG before the GPU is touched.  Integer arithmetic and copies only: results are
+ * bit-identical from run to run and do not depend on the other images.
+ *
+ * hp_resize_rgb     Image.resize(size, BILINEAR | BICUBIC, box) of 8-bit RGB, d_in [B][in_h][in_w][3] -> d_out [B][out_h][out_w][3]
+ *                   (pinned against Pillow 12.2 by tests/golden/g15_resize.npz).  Per axis, with in = the (cropped) image's size,
+ *                   box = (b0, b1) and out the output size, in double:  scale = (b1 - b0) / out, fscale = max(scale, 1),
+ *                   support = S fscale (S = 1 bilinear, 2 bicubic); for output index i: centre = b0 + (i + 0.5) scale,
+ *                   lo = max((int)(centre - support + 0.5), 0), hi = min((int)(centre + support + 0.5), in); the weight of source j
+ *                   in [lo, hi) is f((j - centre + 0.5) / fscale), f the triangle or the cubic with a = -0.5, divided by the
+ *                   window's sum, then rounded to fixed point: (int)(w 2^22 + 0.5), (int)(w 2^22 - 0.5) below zero.
+ *                     d_xbounds [n_tables][out_w][2] = (lo + the crop's origin, hi - lo),  d_xweights [n_tables][out_w][ksize_x]
+ *                   and the same along y.  A pass is  out = clip((2^21 + sum_k weights[i][k] in[lo + k]) >> 22, 0, 255)  in 32-bit
+ *                   signed integers (arithmetic shift).  The pass along x runs first into a uint8 intermediate
+ *                   [B][in_h][out_w][3] in d_workspace (only the rows the pass along y reads), then the pass along y.  Pillow
+ *                   skips a pass whose axis keeps its size with the whole axis as box; the host says so with ksize_x == 0
+ *                   (then out_w == in_w) or ksize_y == 0 (then out_h == in_h), the tables of a skipped pass may be NULL, and a
+ *                   call with both skipped copies the frames.  (A skipped pass would be the identity: its weights are 2^22 on
+ *                   one tap.)  band_x: the host's bound on the source pixels one tile of 256 consecutive output pixels covers,
+ *                   max over tiles and table sets of (lo + n of the tile's last index) - (lo of its first); the pass along x
+ *                   stages that band in the LDS.  band_x > 12288, or a ksize > 4096, is HP_ERR_ARG and launches nothing; a band
+ *                   smaller than the tables need is not an overrun, the taps beyond it read 0.
+ *                   d_workspace: hp_resize_workspace_bytes(B, in_h, out_w) = roundup8(3 B in_h out_w) bytes (-1 for sizes out of
+ *                   range), needed only when both passes run.
+ * hp_resize_nearest Image.resize(size, NEAREST, box) of modes I and F: d_in / d_out are 4-byte pixels copied as bits (NaN, negative
+ *                   depths and negative ids pass through).  d_xindex [n_tables][out_w], d_yindex [n_tables][out_h]: the source
+ *                   index of every output index, (int) t_i with t_0 = b0 + scale / 2 and t_{i + 1} = t_i + scale -- a RUNNING sum in
+ *                   double, as Pillow tabulates it -- plus the crop's origin; an index outside the frame (-1 included) gives 0.
+ * hp_seg_boxes      d_segmentation [B][h][w] int32, d_ids [B][max_ids] int32, d_count [B] (clamped to 0 .. max_ids), 1 <= max_ids
+ *                   <= 256.  d_boxes [B][max_ids][4] int32 = (x1, y1, x2, y2), the INCLUSIVE min and max of the columns and rows
+ *                   where segmentation == ids[b][k], as the reference's make_detections_from_segmentation; d_n_px [B][max_ids] the
+ *                   number of such pixels.  A slot whose id is absent, or at or above d_count[b], has n_px 0 and an unspecified
+ *                   box.  An id listed twice is counted in its first slot.  Integer min / max / add reductions in the LDS per
+ *                   workgroup, then integer atomics on the table: exact whatever the order.
+ * ---------------------------------------------------------------------------------- */
+int64_t hp_resize_workspace_bytes(int B, int in_h, int out_w);
+int hp_resize_rgb(int B, int in_h, int in_w, int out_h, int out_w, const uint8_t* d_in, int n_tables, const int32_t* d_table_of,
+                  const int32_t* d_xbounds, const int32_t* d_xweights, int ksize_x, int band_x, const int32_t* d_ybounds,
+                  const int32_t* d_yweights, int ksize_y, const uint8_t* d_apply, uint8_t* d_out, void* d_workspace,
+                  int64_t workspace_bytes, void* stream);
+int hp_resize_nearest(int B, int in_h, int in_w, int out_h, int out_w, const void* d_in, int n_tables, const int32_t* d_table_of,
+                      const int32_t* d_xindex, const int32_t* d_yindex, const uint8_t* d_apply, void* d_out, void* stream);
+int hp_seg_boxes(int B, int h, int w, const int32_t* d_segmentation, const int32_t* d_ids, const int32_t* d_count, int max_ids,
+                 int32_t* d_boxes, int32_t* d_n_px, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

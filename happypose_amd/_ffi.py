@@ -214,6 +214,10 @@ _PROTOS = {
     "hp_resize_nearest": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, c_i32p, c_i32p, c_i32p, c_u8p,
                                     C.c_void_p, C.c_void_p]),
     "hp_seg_boxes": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, C.c_int, c_i32p, c_i32p, C.c_void_p]),
+    "hp_pose_add_noise": (C.c_int, [C.c_int, C.c_int, c_f32p, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, C.c_uint64, c_f32p,
+                                    c_f32p, c_f32p, C.c_void_p]),
+    "hp_tco_init_from_boxes": (C.c_int, [C.c_int, c_f32p, C.c_int, c_i32p, c_f32p, C.c_int, c_i32p, C.c_float, C.c_float, c_f32p,
+                                         C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

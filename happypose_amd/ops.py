@@ -1233,6 +1233,70 @@ def loss_refiner_backward(TCO_possible_gt: torch.Tensor, TCO_input: torch.Tensor
     return (grad, grad_parts) if return_parts else grad
 
 
+# ---- training hypotheses (csrc/train_hyp.hip) ------------------------------------------------------------------------------------
+def _on_device(what: str, **tensors) -> torch.device:
+    """Every given tensor lives on one GPU (there is no CPU path): its device."""
+    dev = None
+    for name, t in tensors.items():
+        if t is None:
+            continue
+        if not isinstance(t, torch.Tensor) or not t.is_cuda or (dev is not None and t.device != dev):
+            where = t.device if isinstance(t, torch.Tensor) else type(t).__name__
+            raise ValueError(f"{what}: {name} is on {where}; every input lives on one GPU (happypose_amd has no CPU path)")
+        dev = t.device
+    return dev
+
+
+def pose_add_noise(TCO: torch.Tensor, euler_deg_std=(15, 15, 15), trans_std=(0.01, 0.01, 0.05), *, seed: int = 0, row_offset: int = 0,
+                   repeat: int = 1, noise: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None,
+                   return_noise: bool = False):
+    """``hp_pose_add_noise``: ``TCO [m, 4, 4]`` -> ``[m * repeat, 4, 4]``, row ``i`` a noisy copy of pose ``i // repeat``.
+    ``noise [m * repeat, 6]`` (angles in radians, metres) is used as it is; without it the noise is drawn from
+    ``(seed, row_offset + i)`` with the given standard deviations.  ``out`` may be ``TCO`` itself when ``repeat == 1``.
+    ``return_noise``: also the six values of every row ``[m * repeat, 6]``."""
+    dev = _on_device("pose_add_noise", TCO=TCO, noise=noise, out=out)
+    assert TCO.dim() == 3 and TCO.shape[1:] == (4, 4), "pose_add_noise: TCO [m, 4, 4]"
+    assert repeat >= 1, "pose_add_noise: repeat >= 1"
+    assert 0 <= seed < 2 ** 64 and 0 <= row_offset < 2 ** 64, "pose_add_noise: seed and row_offset are unsigned 64-bit integers"
+    n = TCO.shape[0] * repeat
+    assert n < 2 ** 31, "pose_add_noise: at most 2^31 - 1 rows"
+    TCO = _f32(TCO, dev)
+    if out is None:
+        out = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
+    assert out.shape == (n, 4, 4) and out.dtype == torch.float32 and out.is_contiguous(), "pose_add_noise: out [m * repeat, 4, 4] float32"
+    std = (C.c_float * 3)(*[float(v) for v in euler_deg_std]), (C.c_float * 3)(*[float(v) for v in trans_std])
+    if noise is not None:
+        assert noise.shape == (n, 6), "pose_add_noise: noise [m * repeat, 6]"
+        noise = _f32(noise, dev)
+    noise_out = torch.empty(n, 6, dtype=torch.float32, device=dev) if return_noise else None
+    with torch.cuda.device(dev):
+        check(lib().hp_pose_add_noise(n, repeat, ptr(TCO), std[0], std[1], seed, row_offset, ptr(noise), ptr(out), ptr(noise_out),
+                                      stream_ptr(dev)), "hp_pose_add_noise")
+    return (out, noise_out) if return_noise else out
+
+
+def tco_init_from_boxes(boxes: torch.Tensor, K: torch.Tensor, z_range=(1.0, 1.0), im_ids=None, box_ids=None) -> torch.Tensor:
+    """``hp_tco_init_from_boxes``: one pose per row of ``im_ids`` / ``box_ids`` (without either: per box, box ``i`` with ``K[i]``)."""
+    dev = _on_device("tco_init_from_boxes", boxes=boxes, K=K)
+    assert len(z_range) == 2
+    assert boxes.dim() == 2 and boxes.shape[-1] == 4 and K.dim() == 3 and K.shape[1:] == (3, 3)
+    n = len(im_ids) if im_ids is not None else len(box_ids) if box_ids is not None else boxes.shape[0]
+    assert box_ids is not None or boxes.shape[0] == n, "one box per row unless box_ids is given"
+    assert im_ids is not None or K.shape[0] == n, "one intrinsics matrix per row unless im_ids is given"
+    _check_ids(im_ids, K.shape[0], "tco_init_from_boxes: im_ids -> K")
+    _check_ids(box_ids, boxes.shape[0], "tco_init_from_boxes: box_ids -> boxes")
+    boxes, K = _f32(boxes, dev), _f32(K, dev)
+    im_ids = None if im_ids is None else _i32(im_ids, dev)
+    box_ids = None if box_ids is None else _i32(box_ids, dev)
+    assert (im_ids is None or im_ids.shape == (n,)) and (box_ids is None or box_ids.shape == (n,))
+    out = torch.empty(n, 4, 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_tco_init_from_boxes(n, ptr(boxes), boxes.shape[0], ptr(box_ids), ptr(K), K.shape[0], ptr(im_ids),
+                                           C.c_float(z_range[0]), C.c_float(z_range[1]), ptr(out), stream_ptr(dev)),
+              "hp_tco_init_from_boxes")
+    return out
+
+
 # --------------------------------------------------------------------------------------------------------------- scenes (scene.hip)
 SCENE_VIS_FIELDS = 10  # HP_SCENE_VIS_FIELDS
 SCENE_MAX_DILATE = 3   # HP_SCENE_MAX_DILATE

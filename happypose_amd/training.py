@@ -1,0 +1,333 @@
+"""The trainers' forward-loss step on the device: a batch in, the reference's validation numbers and the gradient at the network's
+output out.
+
+Names and argument orders are the reference's: ``h_pose`` (``CP/training/pose_forward_loss.py``), ``megapose_forward_loss``
+(``MP/training/megapose_forward_loss.py``), ``add_noise`` (``TB/lib3d/transform_ops.py:70-104``), ``TCO_init_from_boxes`` and
+``TCO_init_from_boxes_zup_autodepth`` (``TB/lib3d/cosypose_ops.py:159-283``).  The hypotheses are made by ``csrc/train_hyp.hip``
+(``ops.pose_add_noise``, ``ops.tco_init_from_boxes``) and ``ops.tco_init_autodepth``, the predictor is one of this library's, the
+losses are ``happypose_amd.losses``: every input and every intermediate stays on the device.
+
+This is the step, not a trainer.  Each iteration's ``network_outputs["pose"]`` is marked ``requires_grad_()`` before the loss, so
+``loss.backward()`` leaves ``dL/dpose`` in its ``.grad`` (``debug_dict["outputs"]["iteration=k"].network_outputs["pose"].grad``):
+the hand-over point for whatever trains a head.  Nothing here runs a network backward or an optimiser.
+
+Differences from the reference, all deliberate:
+
+* random numbers: the reference draws from the global ``np.random`` stream; here every draw is a function of an explicit ``seed``
+  (Philox4x32-10 for the pose noise, ``RandomState(seed)`` for the ids of the loss points) and repeats bit for bit.  The
+  reference's stream is not reproduced;
+* sequence: the reference reads every meter value back with ``.item()`` -- ``4 n_iterations + 2`` synchronisations a step; here
+  the values are collected on the device and read back once, after the loss is formed.  The values and their order of addition
+  to the meters are the reference's;
+* ``n_hypotheses`` copies of a ground truth are made inside the noise launch, images and intrinsics are indexed per hypothesis
+  (``im_ids``) instead of gathered;
+* the auto-depth initialisations use the deterministic point subset of the estimators (``MeshStore.point_ids``) where the
+  reference samples one at random;
+* not built: ``coarse_classif_multiview_paper`` (its ``sphere_26views`` cannot be pinned) and with it the
+  rendered-views-logits loss, ``n_pose_dims == 7`` (no quaternion loss kernel), ``random_ambient_light``, and the bokeh
+  visualisation (``make_visualization=True`` raises).
+"""
+
+from __future__ import annotations
+
+import math
+from dataclasses import dataclass
+from typing import Any, Dict, List, Optional, Sequence, Tuple
+
+import numpy as np
+import torch
+
+from . import losses, ops
+
+__all__ = ["AverageValueMeter", "TrainingConfig", "CosyPoseTrainingConfig", "add_noise", "TCO_init_from_boxes",
+           "TCO_init_from_boxes_zup_autodepth", "make_hypotheses", "h_pose", "megapose_forward_loss"]
+
+MEGAPOSE_METHODS = ("coarse_z_up+auto-depth", "refiner_gt+noise")
+COSYPOSE_METHODS = ("fixed", "gt+noise", "fixed+trans_noise")
+AUTODEPTH_POINTS = 200  # MP/training/megapose_forward_loss.py:83-85
+
+
+class AverageValueMeter:
+    """What the forward-loss functions need of ``torchnet.meter.AverageValueMeter``: ``add(value, n=1)``, ``value() -> (mean,
+    std)``, ``reset()`` and the fields ``n``, ``sum``, ``mean``, ``std``."""
+
+    def __init__(self):
+        self.reset()
+
+    def reset(self) -> None:
+        self.n, self.sum, self._sq = 0, 0.0, 0.0
+        self.mean, self.std = math.nan, math.nan
+
+    def add(self, value: float, n: int = 1) -> None:
+        self.n += n
+        self.sum += value
+        self._sq += value * value
+        self.mean = self.sum / self.n
+        if self.n == 1:
+            self.std = math.inf
+        else:  # unbiased, from the running sums
+            self.std = math.sqrt(max(self._sq - self.n * self.mean * self.mean, 0.0) / (self.n - 1.0))
+
+    def value(self) -> Tuple[float, float]:
+        return self.mean, self.std
+
+
+@dataclass
+class TrainingConfig:
+    """The fields ``megapose_forward_loss`` reads, with the defaults of ``MP/training/training_config.py`` -- but for
+    ``random_ambient_light`` (reference: True), which this renderer does not offer: True raises."""
+
+    hypotheses_init_method: str = "refiner_gt+noise"
+    n_hypotheses: int = 1
+    init_euler_deg_std: Tuple[float, float, float] = (15, 15, 15)
+    init_trans_std: Tuple[float, float, float] = (0.01, 0.01, 0.05)
+    random_ambient_light: bool = False
+    n_points_loss: int = 2000
+    loss_alpha_pose: float = 1.0
+    predict_pose_update: bool = True
+    predict_rendered_views_logits: bool = False
+
+
+@dataclass
+class CosyPoseTrainingConfig:
+    """The fields ``h_pose`` reads, with the values of ``CP/scripts/run_pose_training.py``."""
+
+    n_points_loss: int = 2600
+    loss_disentangled: bool = True
+    n_pose_dims: int = 9
+    init_method: str = "v0"
+
+
+# ---- primitives -------------------------------------------------------------------------------------------------------------------
+def add_noise(TCO: torch.Tensor, euler_deg_std=(15, 15, 15), trans_std=(0.01, 0.01, 0.05), *, seed: int, row_offset: int = 0,
+              repeat: int = 1, return_noise: bool = False):
+    """``TCO [m, 4, 4]`` on the device -> ``[m * repeat, 4, 4]``: ``R R_noise``, ``t + dt`` with ``R_noise = euler2mat`` (static
+    xyz) of normal angles (degrees) and normal ``dt`` (metres).  Row ``i`` is drawn from ``(seed, row_offset + i)`` alone
+    (``hp_pose_add_noise`` in ``include/happypose_amd.h`` states the counter layout); a standard deviation of 0 leaves that part
+    of the pose bit for bit.  ``return_noise``: also ``[m * repeat, 6]``, the angles in radians and ``dt``."""
+    return ops.pose_add_noise(TCO, euler_deg_std, trans_std, seed=seed, row_offset=row_offset, repeat=repeat, return_noise=return_noise)
+
+
+def TCO_init_from_boxes(z_range, boxes: torch.Tensor, K: torch.Tensor) -> torch.Tensor:
+    """Identity rotation at depth ``mean(z_range)`` behind the box centre: ``[B, 4, 4]``."""
+    assert len(z_range) == 2
+    assert boxes.dim() == 2 and boxes.shape[-1] == 4
+    return ops.tco_init_from_boxes(boxes, K, z_range)
+
+
+def TCO_init_from_boxes_zup_autodepth(boxes_2d: torch.Tensor, store, K: torch.Tensor, *, labels: Sequence[str],
+                                      n_points: Optional[int] = None) -> torch.Tensor:
+    """z-up rotation, depth from the extent of the object's points against the box (``ops.tco_init_autodepth``).  Where the
+    reference takes ``model_points_3d``, this takes the ``MeshStore`` that holds the point table on the device and the
+    ``labels`` of the rows; ``n_points``: the deterministic subset of that many points (None: all)."""
+    if not isinstance(store, ops.MeshStore):
+        raise TypeError("TCO_init_from_boxes_zup_autodepth: the kernel reads the point table of a MeshStore (model.store), "
+                        "not a tensor of points")
+    ops._on_device("TCO_init_from_boxes_zup_autodepth", boxes_2d=boxes_2d, K=K)
+    n = boxes_2d.shape[0]
+    assert len(labels) == n and K.shape[0] == n
+    ids = torch.arange(n, dtype=torch.int32, device=store.device)
+    return ops.tco_init_autodepth(store, boxes_2d, K, ids, store.ids_of(list(labels)), n_points=n_points)
+
+
+# ---- the batch ----------------------------------------------------------------------------------------------------------------------
+def _labels(data) -> List[str]:
+    if getattr(data, "object_datas", None) is not None:
+        return [o["label"] if isinstance(o, dict) else o.label for o in data.object_datas]
+    return [str(l) for l in data.labels]
+
+
+def _batch(data, what: str) -> Dict[str, Any]:
+    """``rgbs`` (uint8 ``[B, 3, H, W]``, or an ``ObservationBatch`` whose ``rgb`` is ``[B, H, W, 3]``), ``depths``, ``K``,
+    ``TCO``, ``bboxes`` as float32 tensors on one device, and the labels."""
+    rgbs, depths = data.rgbs, getattr(data, "depths", None)
+    if hasattr(rgbs, "rgb"):  # ObservationBatch
+        depths = rgbs.depth if depths is None else depths
+        rgbs = rgbs.rgb.permute(0, 3, 1, 2)
+    dev = ops._on_device(what, rgbs=rgbs, depths=depths, K=data.K, TCO=data.TCO, bboxes=data.bboxes)
+    assert rgbs.dim() == 4 and rgbs.shape[1] == 3 and rgbs.dtype == torch.uint8, f"{what}: rgbs uint8 [B, 3, H, W]"
+    b = rgbs.shape[0]
+    labels = _labels(data)
+    K, TCO, bboxes = data.K.float(), data.TCO.float(), data.bboxes.float()
+    assert K.shape == (b, 3, 3) and TCO.shape == (b, 4, 4) and bboxes.shape == (b, 4) and len(labels) == b, f"{what}: one object per image"
+    return dict(rgbs=rgbs, depths=depths, K=K.contiguous(), TCO=TCO.contiguous(), bboxes=bboxes.contiguous(), labels=labels, device=dev, B=b)
+
+
+def _images(bt, input_depth: bool) -> torch.Tensor:
+    """``cast_images``: rgb in [0, 1], the depth (metres) as a fourth channel when the model reads one."""
+    images = bt["rgbs"].float() / 255.0
+    if input_depth:
+        assert bt["depths"] is not None, "the model reads depth: data.depths [B, H, W]"
+        d = bt["depths"].float()
+        images = torch.cat([images, d.reshape(bt["B"], 1, *images.shape[-2:])], dim=1)
+    return images.contiguous()
+
+
+def _loss_tables(mesh_db, labels, TCO_gt: torch.Tensor, n_points: int, seed: int):
+    """``points [B, n_points, 3]`` (a seeded subset of the padded table, the same ids for every object as in the reference) and
+    ``TCO_possible_gt [B, S, 4, 4] = TCO_gt @ symmetries``."""
+    meshes = mesh_db.select(labels)
+    if not isinstance(meshes.points, torch.Tensor) or not meshes.points.is_cuda:
+        raise ValueError("mesh_db lives on the host: pass MeshDataBase.from_object_ds(ds).batched().to(device)")
+    n_pad = meshes.points.shape[1]
+    assert n_points <= n_pad, f"n_points_loss = {n_points} but the objects have {n_pad} points"
+    ids = np.random.RandomState(seed & 0xFFFFFFFF).choice(n_pad, size=n_points, replace=False)
+    points = meshes.points[:, torch.as_tensor(ids, device=meshes.points.device)].float().contiguous()
+    sym = meshes.symmetries.float()
+    # T_gt @ S as products and sums of elementwise kernels: a fixed order of additions, no BLAS
+    possible = (TCO_gt[:, None, :, :, None] * sym[:, :, None, :, :]).sum(3)
+    return points, possible.contiguous()
+
+
+def _seed(seed: int, stream: int) -> int:
+    """One 64-bit Philox key per use of ``seed`` inside a step."""
+    return (int(seed) * 0x9E3779B97F4A7C15 + stream) & 0xFFFFFFFFFFFFFFFF
+
+
+def make_hypotheses(method: str, data, mesh_db, cfg, seed: int, *, store=None) -> torch.Tensor:
+    """The initial hypotheses of a step, ``[B, n_hypotheses, 4, 4]`` on the device.  MegaPose's ``cfg.hypotheses_init_method``:
+    ``"coarse_z_up+auto-depth"`` (one hypothesis), ``"refiner_gt+noise"``; CosyPose's ``input_generator``: ``"fixed"``,
+    ``"gt+noise"``, ``"fixed+trans_noise"`` (one hypothesis each).  ``store``: the predictor's ``MeshStore``, for the auto-depth
+    methods.  ``mesh_db`` is not read by the methods that are built; it keeps the reference's place in the argument list."""
+    if method == "coarse_classif_multiview_paper":
+        raise NotImplementedError("coarse_classif_multiview_paper needs sphere_26views, which cannot be pinned (DESIGN.md 8)")
+    if method == "coarse_classif_multiview_SO3_grid":
+        raise NotImplementedError
+    if method not in MEGAPOSE_METHODS + COSYPOSE_METHODS:
+        raise ValueError("Unknown hypotheses method", method)
+    bt = data if isinstance(data, dict) and "B" in data else _batch(data, "make_hypotheses")
+    B, key = bt["B"], _seed(seed, 1)
+    if method == "refiner_gt+noise":
+        n_hyp = int(cfg.n_hypotheses)
+        return add_noise(bt["TCO"], cfg.init_euler_deg_std, cfg.init_trans_std, seed=key, repeat=n_hyp).view(B, n_hyp, 4, 4)
+    if method == "gt+noise":
+        return add_noise(bt["TCO"], (15, 15, 15), (0.01, 0.01, 0.05), seed=key).view(B, 1, 4, 4)
+    if method == "fixed":
+        return TCO_init_from_boxes((1.0, 1.0), bt["bboxes"], bt["K"]).view(B, 1, 4, 4)
+    # z-up + auto-depth, then translation noise only
+    if method == "coarse_z_up+auto-depth":
+        assert cfg.n_hypotheses == 1
+        n_points = AUTODEPTH_POINTS
+    else:
+        assert cfg.init_method == "z-up+auto-depth"
+        n_points = int(cfg.n_points_loss)
+    if store is None:
+        raise ValueError(f"make_hypotheses: {method!r} reads the point table of the predictor's MeshStore: pass store=model.store")
+    init = TCO_init_from_boxes_zup_autodepth(bt["bboxes"], store, bt["K"], labels=bt["labels"], n_points=min(n_points, store.n_pad))
+    return ops.pose_add_noise(init, (0, 0, 0), (0.01, 0.01, 0.05), seed=key, out=init).view(B, 1, 4, 4)
+
+
+def _read_back(meters, keyed: List[Tuple[str, torch.Tensor]]) -> None:
+    """The step's one read-back: the device scalars in one transfer, then the meters in the reference's order."""
+    if keyed:
+        for (key, _), v in zip(keyed, torch.stack([v.detach().reshape(()) for _, v in keyed]).tolist()):
+            meters[key].add(v)
+
+
+def _run_model(model, images, K, labels, hyp, n_iterations, **kw):
+    B, n_hyp = hyp.shape[:2]
+    im_ids = torch.arange(B, dtype=torch.int32, device=hyp.device).repeat_interleave(n_hyp)
+    labels_h = [l for l in labels for _ in range(n_hyp)]
+    return model(images=images, K=K, labels=labels_h, TCO=hyp.reshape(B * n_hyp, 4, 4), n_iterations=n_iterations, im_ids=im_ids, **kw)
+
+
+# ---- CosyPose ---------------------------------------------------------------------------------------------------------------------
+def h_pose(model, mesh_db, data, meters, cfg, n_iterations: int = 1, input_generator: str = "fixed", *, seed: int = 0,
+           debug_dict: Optional[Dict[str, Any]] = None) -> torch.Tensor:
+    """One forward-loss step of the CosyPose trainer: fills ``loss_TCO-iter=k``, ``loss_TCO`` and ``loss_total`` and returns the
+    loss as a device scalar.  With ``cfg.loss_disentangled`` the gradient arrives at each iteration's
+    ``network_outputs["pose"]``; with the ADD-L1 loss at its ``TCO_output``.  ``debug_dict`` (not in the reference) receives
+    ``outputs``, ``hypotheses_TCO_init``, ``points`` and ``TCO_possible_gt``."""
+    if cfg.loss_disentangled:
+        if cfg.n_pose_dims == 7:
+            raise NotImplementedError("n_pose_dims == 7: there is no quaternion loss kernel")
+        if cfg.n_pose_dims != 9:
+            raise ValueError(cfg.n_pose_dims)
+    bt = _batch(data, "h_pose")
+    images = _images(bt, False)
+    points, TCO_possible_gt = _loss_tables(mesh_db, bt["labels"], bt["TCO"], int(cfg.n_points_loss), _seed(seed, 0))
+    hyp = make_hypotheses(input_generator, bt, mesh_db, cfg, seed, store=getattr(model, "store", None))
+    outputs = _run_model(model, images, bt["K"], bt["labels"], hyp, n_iterations)
+
+    keyed, losses_TCO_iter = [], []
+    for n in range(n_iterations):
+        it = outputs[f"iteration={n + 1}"]
+        if cfg.loss_disentangled:
+            pose = it.network_outputs["pose"].requires_grad_()
+            loss_TCO_iter = losses.loss_refiner_CO_disentangled(TCO_possible_gt=TCO_possible_gt, TCO_input=it.TCO_input,
+                                                                refiner_outputs=pose, K_crop=it.K_crop, points=points)
+        else:
+            loss_TCO_iter = losses.compute_ADD_L1_loss(TCO_possible_gt[:, 0], it.TCO_output.requires_grad_(), points)
+        keyed.append((f"loss_TCO-iter={n + 1}", loss_TCO_iter.mean()))
+        losses_TCO_iter.append(loss_TCO_iter)
+    loss_TCO = torch.cat(losses_TCO_iter).mean()
+    loss = loss_TCO
+    keyed += [("loss_TCO", loss_TCO), ("loss_total", loss)]
+    _read_back(meters, keyed)
+    if debug_dict is not None:
+        debug_dict.update(outputs=outputs, hypotheses_TCO_init=hyp, points=points, TCO_possible_gt=TCO_possible_gt)
+    return loss
+
+
+# ---- MegaPose ---------------------------------------------------------------------------------------------------------------------
+def megapose_forward_loss(model, cfg, data, meters, mesh_db, n_iterations: int, debug_dict: Optional[Dict[str, Any]],
+                          make_visualization: bool = False, train: bool = True, is_notebook: bool = False, *,
+                          seed: int = 0) -> torch.Tensor:
+    """One forward-loss step of the MegaPose trainer: fills ``loss_TCO-iter=k``, ``loss_TCO-iter=k-loss_orn|loss_xy|loss_z``,
+    ``time_render``, ``loss_TCO`` and ``loss_total`` and returns the loss as a device scalar; the gradient arrives at each
+    iteration's ``network_outputs["pose"]``.  ``debug_dict`` receives the reference's ``outputs`` and ``time_render`` and, beyond
+    them, ``hypotheses_TCO_init [B, n_hypotheses, 4, 4]``, ``points`` and ``TCO_possible_gt`` (per hypothesis row).  ``train``
+    is accepted and, as in the reference, not read."""
+    if make_visualization:
+        raise NotImplementedError("megapose_forward_loss: the bokeh visualisation is not built")
+    if cfg.random_ambient_light:
+        raise NotImplementedError("megapose_forward_loss: random_ambient_light is not built (set cfg.random_ambient_light = False)")
+    if cfg.predict_rendered_views_logits:
+        raise NotImplementedError("megapose_forward_loss: the rendered-views-logits loss needs coarse_classif_multiview_paper")
+    method = cfg.hypotheses_init_method
+    if method not in MEGAPOSE_METHODS and not method.startswith("coarse_classif_multiview"):
+        raise ValueError(method)
+    bt = _batch(data, "megapose_forward_loss")
+    images = _images(bt, bool(getattr(model, "input_depth", False)))
+    B, n_hyp = bt["B"], int(cfg.n_hypotheses)
+    hyp = make_hypotheses(method, bt, mesh_db, cfg, seed, store=getattr(model, "store", None))
+    outputs = _run_model(model, images, bt["K"], bt["labels"], hyp, n_iterations, random_ambient_light=False)
+
+    points, TCO_possible_gt = _loss_tables(mesh_db, bt["labels"], bt["TCO"], int(cfg.n_points_loss), _seed(seed, 0))
+    TCO_possible_gt = TCO_possible_gt.repeat_interleave(n_hyp, dim=0)
+    points = points.repeat_interleave(n_hyp, dim=0)
+
+    keyed, list_losses_pose, time_render = [], [], 0.0
+    for n in range(n_iterations):
+        it = outputs[f"iteration={n + 1}"]
+        if cfg.predict_pose_update:
+            pose = it.network_outputs["pose"].requires_grad_()
+            loss_TCO_iter, loss_data = losses.loss_refiner_CO_disentangled_reference_point(
+                TCO_possible_gt=TCO_possible_gt, TCO_input=it.TCO_input, refiner_outputs=pose, K_crop=it.K_crop, points=points, tCR=it.tCR)
+            loss_TCO_iter = loss_TCO_iter.view(B, n_hyp)
+            keyed.append((f"loss_TCO-iter={n + 1}", loss_TCO_iter.mean()))
+            list_losses_pose.append(loss_TCO_iter)
+            for key, val in loss_data.items():
+                if key != "loss":
+                    keyed.append((f"loss_TCO-iter={n + 1}-{key}", val.view(B, n_hyp).mean()))
+        time_render += it.timing_dict["render"]
+
+    loss_hypotheses = torch.zeros((B, n_hyp, n_iterations), device=bt["device"], dtype=torch.float32)
+    if cfg.predict_pose_update:
+        losses_pose = torch.stack(list_losses_pose).permute(1, 2, 0)
+        loss_hypotheses = loss_hypotheses + cfg.loss_alpha_pose * losses_pose
+        keyed.append(("loss_TCO", losses_pose.mean(dim=(-1, -2)).mean()))
+    loss = loss_hypotheses.mean()
+    keyed.append(("loss_total", loss))
+
+    # the reference's order: the iterations' meters, time_render, loss_TCO, loss_total
+    n_iter_keys = len(keyed) - (2 if cfg.predict_pose_update else 1)
+    values = torch.stack([v.detach().reshape(()) for _, v in keyed]).tolist()  # the step's one read-back
+    for (key, _), v in list(zip(keyed, values))[:n_iter_keys]:
+        meters[key].add(v)
+    meters["time_render"].add(time_render)
+    for (key, _), v in list(zip(keyed, values))[n_iter_keys:]:
+        meters[key].add(v)
+    if debug_dict is not None:
+        debug_dict.update(outputs=outputs, time_render=time_render, hypotheses_TCO_init=hyp, points=points, TCO_possible_gt=TCO_possible_gt)
+    return loss

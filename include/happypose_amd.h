@@ -1209,6 +1209,47 @@ int hp_resize_nearest(int B, int in_h, int in_w, int out_h, int out_w, const voi
 int hp_seg_boxes(int B, int h, int w, const int32_t* d_segmentation, const int32_t* d_ids, const int32_t* d_count, int max_ids,
                  int32_t* d_boxes, int32_t* d_n_px, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Hypothesis generation of the trainers' forward-loss step (csrc/train_hyp.hip; the user-facing layer is
+ * happypose_amd/training.py).  Replaces add_noise (TB/lib3d/transform_ops.py:70-104 == CP/lib3d/transform_ops.py, a host loop over
+ * transforms3d.euler.euler2mat) and TCO_init_from_boxes (TB/lib3d/cosypose_ops.py:159-181 == CP/lib3d/cosypose_ops.py:146-168).
+ * One thread per output row, no atomics: a row is a function of its own inputs and bit-identical from run to run.
+ *
+ * hp_pose_add_noise       d_TCO [n / repeat][4][4], d_TCO_out [n][4][4]: output row i is a noisy copy of pose i / repeat (repeat >= 1
+ *                         divides n: the n_hypotheses copies per image are made inside the launch).  d_TCO_out may be d_TCO itself
+ *                         when repeat == 1; any other overlap is HP_ERR_ARG.
+ *  Noise, given           d_noise_in [n][6] float32 = (ai, aj, ak) in RADIANS, (dx, dy, dz) in metres, used as they are;
+ *                         euler_deg_std / trans_std (HOST arrays of 3) and seed / row_offset are then not read.
+ *  Noise, drawn           d_noise_in == NULL.  row = row_offset + i (64 bits); Philox4x32-10 (constants as for
+ *                         hp_mesh_sample_surface) with key (seed & 0xffffffff, seed >> 32) and the two counters
+ *                         (row & 0xffffffff, row >> 32, j, 0), j = 0, 1, giving the words w[4 j + 0 .. 3].  Pair p = 0, 1, 2:
+ *                           u1 = ((w[2 p] >> 8) + 1) 2^-24 in (0, 1],  u2 = (w[2 p + 1] >> 8) 2^-24 in [0, 1)
+ *                           z[2 p] = sqrt(-2 ln u1) cos(2 pi u2),  z[2 p + 1] = sqrt(-2 ln u1) sin(2 pi u2)
+ *                         (w[6], w[7] unused) and  noise[k] = z[k] euler_deg_std[k] pi / 180,  noise[3 + k] = z[3 + k] trans_std[k],
+ *                         k = 0, 1, 2, evaluated in double and rounded once to float32.  Those six floats go to d_noise_out [n][6]
+ *                         (may be NULL; also written, as a copy, when the noise is given) and into the pose, so a second call with
+ *                         them as d_noise_in gives the same bits.  A row depends on (seed, row_offset + i) and its pose, not on n.
+ *                         A negative or NaN standard deviation is HP_ERR_ARG.
+ *  Pose                   R_noise = euler2mat(ai, aj, ak), static axes xyz ('sxyz'): Rz(ak) Ry(aj) Rx(ai), i.e.
+ *                           [ cy cz   sx sy cz - cx sz   cx sy cz + sx sz ]
+ *                           [ cy sz   sx sy sz + cx cz   cx sy sz - sx cz ]
+ *                           [ -sy     sx cy              cx cy            ]
+ *                         R_out = R R_noise (double from the float32 inputs, each entry rounded once), t_out = t + dt (float32),
+ *                         bottom row copied.  ai == aj == ak == 0 leaves the 3 x 3 block, and dt[k] == 0 leaves t[k], bit for bit:
+ *                         a standard deviation of 0 switches that part of the noise off exactly.
+ * hp_tco_init_from_boxes  row i: box d_boxes[d_box_ids ? d_box_ids[i] : i] = (x1, y1, x2, y2) of d_boxes [n_boxes][4], intrinsics
+ *                         d_K[d_im_ids ? d_im_ids[i] : i] of d_K [n_images][9];  z = (z_lo + z_hi) / 2,
+ *                         t = (((x1 + x2) / 2 - cx) z / fx, ((y1 + y2) / 2 - cy) z / fy, z) in float32 in that order of
+ *                         operations, identity rotation.  An id outside its table gives a NaN pose and reads nothing outside
+ *                         the tables, see hp_pose_prep.
+ * n == 0 returns HP_OK and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+int hp_pose_add_noise(int n, int repeat, const float* d_TCO, const float* euler_deg_std /* host [3] */,
+                      const float* trans_std /* host [3] */, uint64_t seed, uint64_t row_offset, const float* d_noise_in,
+                      float* d_TCO_out, float* d_noise_out, void* stream);
+int hp_tco_init_from_boxes(int n, const float* d_boxes, int n_boxes, const int32_t* d_box_ids, const float* d_K, int n_images,
+                           const int32_t* d_im_ids, float z_lo, float z_hi, float* d_TCO_out, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

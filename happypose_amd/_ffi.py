@@ -218,6 +218,19 @@ _PROTOS = {
                                     c_f32p, c_f32p, C.c_void_p]),
     "hp_tco_init_from_boxes": (C.c_int, [C.c_int, c_f32p, C.c_int, c_i32p, c_f32p, C.c_int, c_i32p, C.c_float, C.c_float, c_f32p,
                                          C.c_void_p]),
+    "hp_det_assign_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
+    "hp_det_assign": (C.c_int, [C.c_int, c_f32p, c_i32p, C.c_int, c_f32p, C.c_int, c_i32p, C.c_float, C.c_float, C.c_int, c_i32p, c_f32p,
+                                C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_det_sample_keys": (C.c_int, [C.c_int, c_i32p, c_i32p, C.c_uint32, C.c_uint64, C.c_void_p, C.c_void_p]),
+    "hp_det_box_encode": (C.c_int, [C.c_int, c_f32p, c_i32p, c_f32p, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, c_f32p,
+                                    C.c_void_p]),
+    "hp_det_mask_targets": (C.c_int, [C.c_int, c_u8p, C.c_int, C.c_int, C.c_int, c_i32p, c_f32p, C.c_int, c_f32p, C.c_void_p]),
+    "hp_det_loss_workspace_bytes": (C.c_int64, [C.c_int]),
+    "hp_loss_rpn": (C.c_int, [C.c_int, C.c_int, c_i32p, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int64,
+                              C.c_void_p]),
+    "hp_loss_fastrcnn": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
+                                   C.c_int64, C.c_void_p]),
+    "hp_loss_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int64, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

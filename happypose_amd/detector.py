@@ -208,7 +208,11 @@ class MaskRCNN:
         return out
 
     # ---- RegionProposalNetwork.forward (eval) -----------------------------------------------------------------
-    def _proposals(self, maps: List[torch.Tensor], b: int):
+    def _proposals(self, maps: List[torch.Tensor], b: int, pre_nms_top_n: Optional[int] = None, post_nms_top_n: Optional[int] = None):
+        """``pre_nms_top_n`` / ``post_nms_top_n``: None = the inference values given at construction (the training step passes
+        torchvision's training values)."""
+        pre = self.cfg["pre"] if pre_nms_top_n is None else int(pre_nms_top_n)
+        post = self.cfg["post"] if post_nms_top_n is None else int(post_nms_top_n)
         H, W = self.size
         dev = self.device
         boxes_l, scores_l, valid_l, lvl_l = [], [], [], []
@@ -216,7 +220,7 @@ class MaskRCNN:
             obj_map, delta_map = maps[5 + l][b], maps[10 + l][b]            # [h,w,4], [h,w,12]
             gh, gw = obj_map.shape[0], obj_map.shape[1]
             ob = obj_map[..., :3].reshape(-1)                               # (y, x, a): torchvision's flattening order
-            k = min(self.cfg["pre"], ob.numel())
+            k = min(pre, ob.numel())
             top, idx = ob.topk(k)
             idx32 = idx.to(torch.int32).contiguous()
             top = top.contiguous()
@@ -235,7 +239,7 @@ class MaskRCNN:
         order = scores.argsort(descending=True, stable=True)
         boxes, scores, lvl = boxes[order], scores[order], lvl[order]
         keep = self._nms(boxes, lvl, self.cfg["rpn_nms"])
-        return boxes[keep][: self.cfg["post"]], scores[keep][: self.cfg["post"]]
+        return boxes[keep][:post], scores[keep][:post]
 
     # ---- MaskRCNN.forward (eval) ------------------------------------------------------------------------------
     @torch.no_grad()

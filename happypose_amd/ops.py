@@ -2134,3 +2134,206 @@ def seg_boxes(segmentation: torch.Tensor, ids, count=None) -> Tuple[torch.Tensor
         with torch.cuda.device(dev):
             check(lib().hp_seg_boxes(B, h, w, ptr(seg), ptr(table), ptr(cnt), max_ids, ptr(boxes), ptr(n_px), stream_ptr(dev)), "hp_seg_boxes")
     return boxes, n_px
+
+
+# ---- the detector's training targets and losses (csrc/det_losses.hip) --------------------------------------------------------------
+def _det_rows(what: str, image_of, n: int, n_images: int, dev) -> torch.Tensor:
+    _det_ids(image_of, n_images, f"{what}: image_of")
+    image_of = _i32(image_of, dev)
+    assert image_of.shape == (n,), f"{what}: image_of [n]"
+    return image_of
+
+
+def _det_device_ids(ids: torch.Tensor, lo: int, hi: int, what: str) -> None:
+    """Index columns that live on the device are range-checked too before the launch that gathers through them (one read-back of
+    two numbers): the training step is not a latency path."""
+    if ids.numel():
+        a, b = torch.stack([ids.min(), ids.max()]).tolist()
+        assert lo <= a and b < hi, f"{what}: ids in [{a}, {b}] outside [{lo}, {hi})"
+
+
+def _det_gt(what: str, gt: torch.Tensor, gt_off, dev):
+    assert gt.dim() == 2 and gt.shape[1] == 4, f"{what}: gt [G, 4] xyxy"
+    off = np.asarray(torch.as_tensor(gt_off).cpu(), dtype=np.int64).reshape(-1)
+    assert off.size >= 2 and off[0] == 0 and off[-1] == gt.shape[0] and (np.diff(off) >= 0).all(), \
+        f"{what}: gt_off [B + 1] ascends from 0 to G"
+    return _f32(gt, dev), torch.as_tensor(off.astype(np.int32), device=dev), off.size - 1
+
+
+def det_assign(boxes: torch.Tensor, image_of, gt: torch.Tensor, gt_off, high: float, low: float,
+               allow_low_quality: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
+    """``hp_det_assign``: torchvision's ``Matcher`` on ``box_iou(gt of the row's image, boxes)`` -> ``(match [n] int32, iou [n])``.
+    ``match`` indexes the batch's ground-truth table ``gt [G, 4]`` (image ``b`` owns rows ``gt_off[b] .. gt_off[b + 1] - 1``);
+    -1 below ``low``, -2 between the thresholds."""
+    dev = _on_device("det_assign", boxes=boxes, gt=gt)
+    assert boxes.dim() == 2 and boxes.shape[1] == 4, "det_assign: boxes [n, 4] xyxy"
+    n = boxes.shape[0]
+    gt, off, n_images = _det_gt("det_assign", gt, gt_off, dev)
+    image_of = _det_rows("det_assign", image_of, n, n_images, dev)
+    _det_device_ids(image_of, 0, n_images, "det_assign: image_of")
+    boxes = _f32(boxes, dev)
+    match = torch.empty(n, dtype=torch.int32, device=dev)
+    iou = torch.empty(n, dtype=torch.float32, device=dev)
+    if n == 0:
+        return match, iou
+    G = gt.shape[0]
+    nbytes = int(lib().hp_det_assign_workspace_bytes(n, G))
+    ws = torch.empty(max(nbytes // 4, 1), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_det_assign(n, ptr(boxes), ptr(image_of), n_images, ptr(gt) if G else None, G, ptr(off), C.c_float(high), C.c_float(low),
+                                  int(bool(allow_low_quality)), ptr(match), ptr(iou), ptr(ws), nbytes, stream_ptr(dev)), "hp_det_assign")
+    return match, iou
+
+
+def det_sample_keys(image_of: torch.Tensor, n_images: int, seed: int, stream: int = 0) -> torch.Tensor:
+    """``hp_det_sample_keys``: one Philox word per row ``[n]`` (int64 tensor holding uint32 values), from ``(index of the row
+    within its image, image, stream, seed)`` alone."""
+    dev = _on_device("det_sample_keys", image_of=image_of)
+    n = image_of.shape[0]
+    image_of = _det_rows("det_sample_keys", image_of, n, n_images, dev)
+    assert 0 <= seed < 2 ** 64 and 0 <= stream < 2 ** 32, "det_sample_keys: seed is an unsigned 64-bit, stream a 32-bit integer"
+    keys = torch.empty(n, dtype=torch.int32, device=dev)
+    if n == 0:
+        return keys.to(torch.int64)
+    _det_device_ids(image_of, 0, n_images, "det_sample_keys: image_of")
+    # the index of a row among the rows of its image, whatever the order of the images
+    order = image_of.argsort(stable=True)
+    starts = torch.cumsum(torch.bincount(image_of, minlength=n_images), 0) - torch.bincount(image_of, minlength=n_images)
+    index = torch.empty(n, dtype=torch.int64, device=dev)
+    index[order] = torch.arange(n, device=dev) - starts[image_of[order].long()]
+    index = index.to(torch.int32)
+    with torch.cuda.device(dev):
+        check(lib().hp_det_sample_keys(n, ptr(index), ptr(image_of), stream, seed, ptr(keys), stream_ptr(dev)), "hp_det_sample_keys")
+    return keys.to(torch.int64) & 0xFFFFFFFF
+
+
+def det_sample(labels: torch.Tensor, image_of, n_images: int, batch_size_per_image: int, positive_fraction: float, seed: int,
+               stream: int = 0) -> List[Tuple[torch.Tensor, torch.Tensor]]:
+    """``BalancedPositiveNegativeSampler``: per image ``(positive rows, negative rows)``, ascending row indices of the batch.
+    Positives are ``labels >= 1``, negatives ``labels == 0``; of each class the ``k`` rows with the smallest ``(key, row)`` are
+    kept, ``k_pos = min(n_pos, int(batch_size_per_image * positive_fraction))``, ``k_neg = min(n_neg, batch_size_per_image -
+    k_pos)`` -- torchvision's arithmetic on this library's keys (``det_sample_keys``), not torch's ``randperm`` stream."""
+    dev = _on_device("det_sample", labels=labels)
+    n = labels.shape[0]
+    image_of = _det_rows("det_sample", image_of, n, n_images, dev)
+    keys = det_sample_keys(image_of, n_images, seed, stream)
+    rows = torch.arange(n, device=dev)
+    composite = keys * (1 << 31) + rows  # (key, row): rows < 2^31
+    num_pos_max = int(batch_size_per_image * positive_fraction)
+    out = []
+    for b in range(n_images):
+        mine = image_of == b
+        pos, neg = rows[mine & (labels >= 1)], rows[mine & (labels == 0)]
+        k_pos = min(pos.numel(), num_pos_max)
+        k_neg = min(neg.numel(), batch_size_per_image - k_pos)
+        pos = pos[composite[pos].argsort()[:k_pos]].sort().values
+        neg = neg[composite[neg].argsort()[:k_neg]].sort().values
+        out.append((pos, neg))
+    return out
+
+
+def det_box_encode(boxes: torch.Tensor, match: torch.Tensor, gt: torch.Tensor, weights=(1.0, 1.0, 1.0, 1.0)) -> torch.Tensor:
+    """``hp_det_box_encode``: ``BoxCoder(weights).encode_single(gt[match], boxes)`` ``[n, 4]``; the zero box where ``match < 0``."""
+    dev = _on_device("det_box_encode", boxes=boxes, match=match, gt=gt)
+    assert boxes.dim() == 2 and boxes.shape[1] == 4 and gt.dim() == 2 and gt.shape[1] == 4, "det_box_encode: boxes [n, 4], gt [G, 4]"
+    n, G = boxes.shape[0], gt.shape[0]
+    assert match.shape == (n,) and len(weights) == 4
+    boxes, gt, match = _f32(boxes, dev), _f32(gt, dev), _i32(match, dev)
+    _det_device_ids(match, -2, G, "det_box_encode: match")
+    out = torch.empty(n, 4, dtype=torch.float32, device=dev)
+    if n:
+        with torch.cuda.device(dev):
+            check(lib().hp_det_box_encode(n, ptr(boxes), ptr(match), ptr(gt) if G else None, G, *[C.c_float(float(w)) for w in weights],
+                                          ptr(out), stream_ptr(dev)), "hp_det_box_encode")
+    return out
+
+
+def det_mask_targets(masks: torch.Tensor, match: torch.Tensor, rois: torch.Tensor, M: int) -> torch.Tensor:
+    """``hp_det_mask_targets``: ``roi_align(masks[match][:, None], rois, (M, M), 1)[:, 0]`` with the adaptive sampling ratio,
+    ``aligned=False``: ``masks [G, H, W]`` uint8, ``rois [n, 4]`` -> ``[n, M, M]`` float32."""
+    dev = _on_device("det_mask_targets", masks=masks, match=match, rois=rois)
+    assert masks.dim() == 3 and masks.dtype in (torch.uint8, torch.bool), "det_mask_targets: masks [G, H, W] uint8"
+    assert rois.dim() == 2 and rois.shape[1] == 4 and match.shape == (rois.shape[0],), "det_mask_targets: rois [n, 4], match [n]"
+    n, (G, H, W) = rois.shape[0], masks.shape
+    out = torch.empty(n, M, M, dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    masks, match, rois = masks.to(torch.uint8).contiguous(), _i32(match, dev), _f32(rois, dev)
+    _det_device_ids(match, 0, G, "det_mask_targets: match")
+    with torch.cuda.device(dev):
+        check(lib().hp_det_mask_targets(n, ptr(masks), G, H, W, ptr(match), ptr(rois), M, ptr(out), stream_ptr(dev)), "hp_det_mask_targets")
+    return out
+
+
+def _det_loss_workspace(rows: int, dev) -> Tuple[torch.Tensor, int]:
+    nbytes = int(lib().hp_det_loss_workspace_bytes(rows))
+    return torch.empty(nbytes // 8, dtype=torch.float64, device=dev), nbytes
+
+
+def loss_rpn(objectness: torch.Tensor, pred_deltas: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor, sampled: torch.Tensor):
+    """``hp_loss_rpn``: ``objectness [A]``, ``pred_deltas [A, 4]``, ``labels [A]`` (>= 1 positive, 0 negative), ``targets [A, 4]``,
+    ``sampled [k]`` distinct rows -> ``(loss [2] = objectness, box, grad_objectness [A], grad_deltas [A, 4])`` for an upstream
+    gradient of 1.  ``k == 0``: zeros."""
+    dev = _on_device("loss_rpn", objectness=objectness, pred_deltas=pred_deltas, labels=labels, targets=targets, sampled=sampled)
+    A = objectness.numel()
+    assert pred_deltas.shape == (A, 4) and labels.shape == (A,) and targets.shape == (A, 4), "loss_rpn: [A], [A, 4], [A], [A, 4]"
+    objectness, pred_deltas, targets = _f32(objectness.reshape(-1), dev), _f32(pred_deltas, dev), _f32(targets, dev)
+    labels, sampled = _i32(labels, dev), _i32(sampled.reshape(-1), dev)
+    k = sampled.numel()
+    _det_device_ids(sampled, 0, A, "loss_rpn: sampled")
+    loss = torch.zeros(2, dtype=torch.float32, device=dev)
+    g_obj = torch.empty(A, dtype=torch.float32, device=dev)
+    g_del = torch.empty(A, 4, dtype=torch.float32, device=dev)
+    if k == 0:
+        return loss, g_obj.zero_(), g_del.zero_()
+    with torch.cuda.device(dev):
+        ws, nbytes = _det_loss_workspace((k + 255) // 256, dev)
+        check(lib().hp_loss_rpn(A, k, ptr(sampled), ptr(objectness), ptr(pred_deltas), ptr(labels), ptr(targets), ptr(loss), ptr(g_obj),
+                                ptr(g_del), ptr(ws), nbytes, stream_ptr(dev)), "hp_loss_rpn")
+    return loss, g_obj, g_del
+
+
+def loss_fastrcnn(class_logits: torch.Tensor, box_regression: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor,
+                  num_classes: Optional[int] = None):
+    """``hp_loss_fastrcnn``: ``class_logits [n, ld]`` of which the first ``num_classes`` columns are classes, ``box_regression
+    [n, >= 4 num_classes]``, ``labels [n]``, ``targets [n, 4]`` -> ``(loss [2] = classifier, box, grad_logits, grad_regression)``
+    in the shapes of the inputs.  ``n == 0``: zeros."""
+    dev = _on_device("loss_fastrcnn", class_logits=class_logits, box_regression=box_regression, labels=labels, targets=targets)
+    assert class_logits.dim() == 2 and box_regression.dim() == 2, "loss_fastrcnn: class_logits [n, ld], box_regression [n, ld_reg]"
+    n, ld = class_logits.shape
+    ld_reg = box_regression.shape[1]
+    Cn = ld if num_classes is None else int(num_classes)
+    assert 1 <= Cn <= ld and 4 * Cn <= ld_reg, "loss_fastrcnn: num_classes <= ld and 4 num_classes <= ld_reg"
+    assert box_regression.shape[0] == n and labels.shape == (n,) and targets.shape == (n, 4), "loss_fastrcnn: one row per proposal"
+    class_logits, box_regression, targets, labels = _f32(class_logits, dev), _f32(box_regression, dev), _f32(targets, dev), _i32(labels, dev)
+    _det_device_ids(labels, 0, Cn, "loss_fastrcnn: labels")
+    loss = torch.zeros(2, dtype=torch.float32, device=dev)
+    g_cls = torch.empty(n, ld, dtype=torch.float32, device=dev)
+    g_reg = torch.empty(n, ld_reg, dtype=torch.float32, device=dev)
+    if n == 0:
+        return loss, g_cls, g_reg
+    with torch.cuda.device(dev):
+        ws, nbytes = _det_loss_workspace((n + 255) // 256, dev)
+        check(lib().hp_loss_fastrcnn(n, Cn, ld, ld_reg, ptr(class_logits), ptr(box_regression), ptr(labels), ptr(targets), ptr(loss),
+                                     ptr(g_cls), ptr(g_reg), ptr(ws), nbytes, stream_ptr(dev)), "hp_loss_fastrcnn")
+    return loss, g_cls, g_reg
+
+
+def loss_mask(mask_logits: torch.Tensor, labels: torch.Tensor, targets: torch.Tensor):
+    """``hp_loss_mask``: ``mask_logits [n, C, M, M]``, ``labels [n]``, ``targets [n, M, M]`` -> ``(loss [1], grad_logits)``.
+    ``n == 0``: a loss of 0, nothing launched."""
+    dev = _on_device("loss_mask", mask_logits=mask_logits, labels=labels, targets=targets)
+    assert mask_logits.dim() == 4 and mask_logits.shape[2] == mask_logits.shape[3], "loss_mask: mask_logits [n, C, M, M]"
+    n, Cn, M, _ = mask_logits.shape
+    assert labels.shape == (n,) and targets.shape == (n, M, M), "loss_mask: labels [n], targets [n, M, M]"
+    mask_logits, targets, labels = _f32(mask_logits, dev), _f32(targets, dev), _i32(labels, dev)
+    _det_device_ids(labels, 0, Cn, "loss_mask: labels")
+    loss = torch.zeros(1, dtype=torch.float32, device=dev)
+    grad = torch.empty(n, Cn, M, M, dtype=torch.float32, device=dev)
+    if n == 0:
+        return loss, grad
+    with torch.cuda.device(dev):
+        ws, nbytes = _det_loss_workspace(n, dev)
+        check(lib().hp_loss_mask(n, Cn, M, ptr(mask_logits), ptr(labels), ptr(targets), ptr(loss), ptr(grad), ptr(ws), nbytes,
+                                 stream_ptr(dev)), "hp_loss_mask")
+    return loss, grad

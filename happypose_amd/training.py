@@ -37,10 +37,10 @@ from typing import Any, Dict, List, Optional, Sequence, Tuple
 import numpy as np
 import torch
 
-from . import losses, ops
+from . import detection_losses, losses, ops
 
-__all__ = ["AverageValueMeter", "TrainingConfig", "CosyPoseTrainingConfig", "add_noise", "TCO_init_from_boxes",
-           "TCO_init_from_boxes_zup_autodepth", "make_hypotheses", "h_pose", "megapose_forward_loss"]
+__all__ = ["AverageValueMeter", "TrainingConfig", "CosyPoseTrainingConfig", "DetectorTrainingConfig", "add_noise", "TCO_init_from_boxes",
+           "TCO_init_from_boxes_zup_autodepth", "make_hypotheses", "h_pose", "megapose_forward_loss", "h_maskrcnn"]
 
 MEGAPOSE_METHODS = ("coarse_z_up+auto-depth", "refiner_gt+noise")
 COSYPOSE_METHODS = ("fixed", "gt+noise", "fixed+trans_noise")
@@ -96,6 +96,17 @@ class CosyPoseTrainingConfig:
     loss_disentangled: bool = True
     n_pose_dims: int = 9
     init_method: str = "v0"
+
+
+@dataclass
+class DetectorTrainingConfig:
+    """The fields ``h_maskrcnn`` reads, with the values of ``CP/scripts/run_detector_training.py:78-82``."""
+
+    rpn_box_reg_alpha: float = 1
+    objectness_alpha: float = 1
+    classifier_alpha: float = 1
+    mask_alpha: float = 1
+    box_reg_alpha: float = 1
 
 
 # ---- primitives -------------------------------------------------------------------------------------------------------------------
@@ -330,4 +341,118 @@ def megapose_forward_loss(model, cfg, data, meters, mesh_db, n_iterations: int, 
         meters[key].add(v)
     if debug_dict is not None:
         debug_dict.update(outputs=outputs, time_render=time_render, hypotheses_TCO_init=hyp, points=points, TCO_possible_gt=TCO_possible_gt)
+    return loss
+
+
+# ---- Mask R-CNN -------------------------------------------------------------------------------------------------------------------
+RPN_TRAIN_TOP_N = (2000, 2000)  # torchvision MaskRCNN: rpn_pre_nms_top_n_train, rpn_post_nms_top_n_train
+MASK_SIZE = 28
+
+
+def _grid_anchors(model, maps) -> torch.Tensor:
+    """``AnchorGenerator`` for one image of the network's canvas: ``[A, 4]`` in torchvision's ``(level, y, x, a)`` order."""
+    dev, out = model.device, []
+    for l in range(5):
+        gh, gw = maps[5 + l].shape[1:3]
+        sy = torch.arange(gh, dtype=torch.int32, device=dev) * (model.padded[0] // gh)
+        sx = torch.arange(gw, dtype=torch.int32, device=dev) * (model.padded[1] // gw)
+        y, x = torch.meshgrid(sy, sx, indexing="ij")
+        shifts = torch.stack([x, y, x, y], -1).reshape(-1, 1, 4).float()
+        out.append((shifts + torch.as_tensor(model._base[l], device=dev).reshape(1, -1, 4)).reshape(-1, 4))
+    return torch.cat(out)
+
+
+def h_maskrcnn(data, model, meters, cfg, *, seed: int = 0, debug_dict: Optional[Dict[str, Any]] = None) -> torch.Tensor:
+    """One forward-loss step of the detector trainer (``CP/training/maskrcnn_forward_loss.py``): the train-mode forward of
+    ``detector.MaskRCNN`` -- torchvision 0.14's ``MaskRCNN.forward`` with targets, restated from its published definitions
+    (parity with torchvision is unpinned: ``happypose_amd.detection_losses``).  ``data = (images, targets)``: uint8 images
+    ``[H, W, 3]`` on the device, one dict ``boxes [g, 4]``, ``labels [g]``, ``masks [g, H, W]`` per image.  Fills
+    ``loss_rpn_box_reg``, ``loss_objectness``, ``loss_box_reg``, ``loss_classifier`` and ``loss_mask`` with one read-back and
+    returns their weighted sum as a device scalar.
+
+    This is the step, not a trainer: the objectness maps, the delta maps, ``class_logits``, ``box_regression`` and
+    ``mask_logits`` are marked ``requires_grad_()`` and left in ``debug_dict`` (not in the reference); after ``loss.backward()``
+    their ``.grad`` is the hand-over point.  No network backward, no optimiser.  The sampler draws from ``seed``; the images must
+    have the network's own size (targets are not resized)."""
+    images, targets = data
+    dev = model.device
+    images = torch.stack(list(images)) if not isinstance(images, torch.Tensor) else images
+    ops._on_device("h_maskrcnn", images=images)
+    assert images.dim() == 4 and images.shape[-1] == 3 and images.dtype == torch.uint8, "h_maskrcnn: images uint8 [H, W, 3]"
+    B, H, W = images.shape[:3]
+    if (H, W) != tuple(model.orig_size) or tuple(model.size) != tuple(model.orig_size):
+        raise NotImplementedError(f"h_maskrcnn: images of {H} x {W} on a network that resizes {model.orig_size} to {model.size}: "
+                                  "targets are not resized")
+    assert len(targets) == B, "h_maskrcnn: one target per image"
+    for t in targets:
+        ops._on_device("h_maskrcnn", boxes=t["boxes"], labels=t["labels"], masks=t["masks"])
+        g = t["boxes"].shape[0]
+        assert t["labels"].shape == (g,) and t["masks"].shape == (g, H, W), "h_maskrcnn: boxes [g, 4], labels [g], masks [g, H, W]"
+    x = (images.permute(0, 3, 1, 2).float() / 255).contiguous()
+
+    # 1. the backbone, FPN and RPN head
+    mb = model.backbone.max_batch
+    chunks = [model.backbone.forward_nhwc(x[s:s + mb]) for s in range(0, B, mb)]
+    maps = [torch.cat([c[i] for c in chunks]) for i in range(15)]
+    objectness_maps = [m.requires_grad_() for m in maps[5:10]]   # [B, h, w, 4]: anchors 0 .. 2, one padding channel
+    delta_maps = [m.requires_grad_() for m in maps[10:15]]       # [B, h, w, 12] = (anchor, 4)
+    maps_d = [m.detach() for m in maps]
+
+    # 2. the RPN losses on all anchors
+    objectness = torch.cat([m[..., :3].reshape(B, -1) for m in objectness_maps], 1).reshape(-1)
+    pred_deltas = torch.cat([m.reshape(B, -1, 4) for m in delta_maps], 1).reshape(-1, 4)
+    anchors = _grid_anchors(model, maps)
+    rpn_labels, rpn_gt_boxes, rpn_matches = detection_losses.rpn_assign_targets_to_anchors([anchors] * B, targets, return_matches=True)
+    rpn_targets = [detection_losses.box_encode(g, anchors, (1.0, 1.0, 1.0, 1.0)) for g in rpn_gt_boxes]
+    seeds = dict(rpn=_seed(seed, 2), box=_seed(seed, 3))
+    loss_objectness, loss_rpn_box_reg, rpn_sampled = detection_losses.rpn_compute_loss(
+        objectness, pred_deltas, rpn_labels, rpn_targets, seed=seeds["rpn"], return_sampled=True)
+
+    # 3. - 5. proposals with the training top-n, the ground truths appended, matched, sampled and encoded
+    with torch.no_grad():
+        rpn_proposals = [model._proposals(maps_d, b, *RPN_TRAIN_TOP_N)[0] for b in range(B)]
+    proposals, matched_idxs, labels, regression_targets = detection_losses.roi_select_training_samples(rpn_proposals, targets, seed=seeds["box"])
+
+    # 6. the box head
+    def rois_of(boxes):
+        return torch.cat([torch.cat([torch.full((p.shape[0], 1), float(b), device=dev), p], 1) for b, p in enumerate(boxes)])
+
+    C_, c4 = model.num_classes, model._c4
+    with torch.no_grad():
+        rois = rois_of(proposals)
+        n = rois.shape[0]
+        pooled = model._roi_align(maps_d, rois, 7)
+        cls, reg = model.box_net.run(pooled) if n else (torch.zeros((0, c4), device=dev), torch.zeros((0, 4 * C_), device=dev))
+    class_logits = cls.reshape(n, -1).clone().requires_grad_()       # [n, c4]: the classes, then padding columns
+    box_regression = reg.reshape(n, -1).clone().requires_grad_()
+    loss_classifier, loss_box_reg = detection_losses.fastrcnn_loss(class_logits, box_regression, labels, regression_targets, num_classes=C_)
+
+    # 7. the mask head on the positive samples
+    pos = [torch.where(l > 0)[0] for l in labels]
+    mask_proposals = [p[i] for p, i in zip(proposals, pos)]
+    pos_matched_idxs = [m[i] for m, i in zip(matched_idxs, pos)]
+    with torch.no_grad():
+        mrois = rois_of(mask_proposals)
+        nm = mrois.shape[0]
+        if nm:
+            ml = model.mask_net.run(model._roi_align(maps_d, mrois, 14))[0]      # [nm, 14, 56, c4] = (i, (j, a, b), class)
+            ml = ml.reshape(nm, 14, 14, 2, 2, -1).permute(0, 5, 1, 3, 2, 4).reshape(nm, -1, MASK_SIZE, MASK_SIZE)[:, :C_]
+        else:
+            ml = torch.zeros((0, C_, MASK_SIZE, MASK_SIZE), device=dev)
+    mask_logits = ml.contiguous().clone().requires_grad_()
+    loss_mask, mask_labels, mask_targets = detection_losses.maskrcnn_loss(
+        mask_logits, mask_proposals, [t["masks"] for t in targets], [t["labels"] for t in targets], pos_matched_idxs, return_targets=True)
+
+    loss = (cfg.rpn_box_reg_alpha * loss_rpn_box_reg + cfg.objectness_alpha * loss_objectness + cfg.box_reg_alpha * loss_box_reg
+            + cfg.classifier_alpha * loss_classifier + cfg.mask_alpha * loss_mask)
+    _read_back(meters, [("loss_rpn_box_reg", loss_rpn_box_reg), ("loss_objectness", loss_objectness), ("loss_box_reg", loss_box_reg),
+                        ("loss_classifier", loss_classifier), ("loss_mask", loss_mask)])
+    if debug_dict is not None:
+        debug_dict.update(objectness_maps=objectness_maps, delta_maps=delta_maps, class_logits=class_logits, box_regression=box_regression,
+                          mask_logits=mask_logits, anchors=anchors, rpn_labels=rpn_labels, rpn_matched_idxs=rpn_matches,
+                          rpn_regression_targets=rpn_targets, rpn_sampled=rpn_sampled, rpn_proposals=rpn_proposals, proposals=proposals,
+                          matched_idxs=matched_idxs, labels=labels, regression_targets=regression_targets, mask_proposals=mask_proposals,
+                          mask_matched_idxs=pos_matched_idxs, mask_labels=mask_labels, mask_targets=mask_targets, seeds=seeds,
+                          losses=dict(loss_rpn_box_reg=loss_rpn_box_reg, loss_objectness=loss_objectness, loss_box_reg=loss_box_reg,
+                                      loss_classifier=loss_classifier, loss_mask=loss_mask))
     return loss

@@ -1250,6 +1250,82 @@ int hp_pose_add_noise(int n, int repeat, const float* d_TCO, const float* euler_
 int hp_tco_init_from_boxes(int n, const float* d_boxes, int n_boxes, const int32_t* d_box_ids, const float* d_K, int n_images,
                            const int32_t* d_im_ids, float z_lo, float z_hi, float* d_TCO_out, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * The detector's training targets and losses (csrc/det_losses.hip; the user-facing layer is happypose_amd/detection_losses.py and
+ * happypose_amd.training.h_maskrcnn).  What torchvision 0.14's train-mode MaskRCNN.forward computes between the networks:
+ * models/detection/rpn.py, roi_heads.py, _utils.py (Matcher, BalancedPositiveNegativeSampler, BoxCoder), ops/boxes.py,
+ * ops/roi_align.py.  torchvision cannot be run beside this library: parity with it is UNPINNED, the definitions below are the
+ * contract and tests/det_losses_ref.py restates them in float64.
+ *
+ * Rows are the boxes of a whole batch: d_image_of [n] int32 names each row's image (0 .. n_images - 1), the ground truths of all
+ * images are one table d_gt [n_gt][4] (x1, y1, x2, y2) and image b owns rows d_gt_off[b] .. d_gt_off[b + 1] - 1 of it
+ * (d_gt_off [n_images + 1], ascending from 0 to n_gt).  Ground-truth indices (d_match) are indices into that table.
+ * Every entry point returns HP_OK and launches nothing when its row count is 0, and HP_ERR_ARG for a negative size, a null
+ * pointer or a workspace that is too small.  No floating-point atomics: sums run per lane in row order, over the wavefront by
+ * shuffles, over the wavefronts in LDS, and over the workgroups' partials in a second launch, so two calls give the same bits and
+ * a row's targets and gradient do not depend on the other rows.  The host layer range-checks every index column before a launch;
+ * the kernels answer an index outside its table with NaN (or background) and touch nothing outside the tables.
+ *
+ * hp_det_assign        Matcher(high, low, allow_low_quality) on box_iou(gt of the row's image, boxes).  IoU in float32 by one
+ *                      device function used by both passes (no contraction): area = (x2 - x1)(y2 - y1) of both, lt = max, rb =
+ *                      min, wh = max(rb - lt, 0), inter = w h, iou = inter / ((a1 + a2) - inter).
+ *                      Pass 1: per ground truth the maximum IoU over the boxes of its image (partials in d_workspace,
+ *                      hp_det_assign_workspace_bytes(n, n_gt) bytes; -1 for negative sizes).  Pass 2: per box the FIRST maximum in
+ *                      ground-truth order (d_iou [n], its IoU); d_match [n] = that ground truth, -1 where the IoU < low, -2 where
+ *                      low <= IoU < high.  allow_low_quality != 0: set_low_quality_matches_ -- every box whose IoU with ANY
+ *                      ground truth of its image EQUALS (float ==, ties included) that ground truth's maximum gets its
+ *                      pre-threshold match back.  An image without ground truths gives -1 and IoU 0 in every row.
+ *                      n_gt <= 65535; low <= high.
+ * hp_det_sample_keys   the seeded half of BalancedPositiveNegativeSampler: d_keys[i] = word 0 of Philox4x32-10 (constants as for
+ *                      hp_mesh_sample_surface) with key (seed & 0xffffffff, seed >> 32) and counter (d_index_in_image[i],
+ *                      d_image_of[i], stream_id, 0).  The selection (the k rows with the smallest (key, index) per image and
+ *                      class) is the host layer's; torch's randperm stream is not reproduced.
+ * hp_det_box_encode    BoxCoder.encode_single with weights (wx, wy, ww, wh): reference box d_gt[d_match[i]], the zero box where
+ *                      d_match[i] is outside 0 .. n_gt - 1; proposal d_boxes[i].  float32, torchvision's order:
+ *                      ex_w = px2 - px1, ex_cx = px1 + 0.5 ex_w, gt_w, gt_cx likewise; dx = wx (gt_cx - ex_cx) / ex_w,
+ *                      dw = ww log(gt_w / ex_w); d_out [n][4] = (dx, dy, dw, dh).
+ * hp_det_mask_targets  project_masks_on_boxes: roi_align(d_masks[d_match[i]], d_rois[i], (M, M), spatial_scale 1, sampling_ratio
+ *                      -1, aligned False).  d_masks [n_gt][h][w] uint8 (its values as floats), d_out [n][M][M] float32.  float32, in
+ *                      the order of torchvision's kernel: roi_w = max(x2 - x1, 1), bin = roi_w / M, grid = ceil(roi_w / M)
+ *                      samples per bin and axis at x1 + pw bin + (ix + 0.5) bin / grid, bilinear taps (0 outside [-1, size],
+ *                      clamped at the borders), summed over iy then ix, divided by the number of samples.  One workgroup per roi.
+ *                      An index outside the table, or a roi that is not finite, gives NaN.
+ * The three losses write the loss and, for an upstream gradient of 1, the gradient with respect to the network's output in the
+ * same pass (the normalisers are known before the launch).  Every term is evaluated in double from the float32 inputs and
+ * accumulated in double; log(1 + exp(-|x|)) is log1p(exp(-|x|)).  A non-finite input in a row makes the loss, and that row's
+ * gradient, NaN.  d_workspace: hp_det_loss_workspace_bytes(rows) bytes with rows = ceil(n_sampled / 256), ceil(n / 256) or n.
+ * hp_loss_rpn          d_sampled [n_sampled] int32: distinct anchor indices.  d_labels [n_anchors] int32 (>= 1 positive, 0
+ *                      negative).  d_loss[0] = mean over the sampled rows of binary_cross_entropy_with_logits(objectness, label >=
+ *                      1); d_loss[1] = sum over the sampled positives of smooth_l1(deltas - targets, beta = 1/9) / n_sampled.
+ *                      d_grad_objectness [n_anchors], d_grad_deltas [n_anchors][4]: zeroed by the call, then the sampled rows.
+ * hp_loss_fastrcnn     d_class_logits [n][ld], n_classes <= ld (columns beyond n_classes are not read; their gradient is 0),
+ *                      d_box_regression [n][ld_reg] (4 n_classes <= ld_reg), d_labels [n] int32 in 0 .. n_classes - 1,
+ *                      d_targets [n][4].  d_loss[0] = mean softmax cross-entropy (row maximum subtracted); d_loss[1] = sum of
+ *                      smooth_l1(beta = 1/9) over the four values of the row's own class for rows with label > 0, / n.
+ * hp_loss_mask         d_mask_logits [n][n_classes][M][M], d_targets [n][M][M]: d_loss[0] = mean over n M M of
+ *                      binary_cross_entropy_with_logits(logits[i][label_i], target_i); the gradient is 0 outside the label's
+ *                      channel.  n == 0 launches nothing (the host layer returns a loss of 0).
+ * ---------------------------------------------------------------------------------- */
+int64_t hp_det_assign_workspace_bytes(int n, int n_gt);
+int hp_det_assign(int n, const float* d_boxes, const int32_t* d_image_of, int n_images, const float* d_gt, int n_gt,
+                  const int32_t* d_gt_off, float high, float low, int allow_low_quality, int32_t* d_match, float* d_iou,
+                  void* d_workspace, int64_t workspace_bytes, void* stream);
+int hp_det_sample_keys(int n, const int32_t* d_index_in_image, const int32_t* d_image_of, uint32_t stream_id, uint64_t seed,
+                       uint32_t* d_keys, void* stream);
+int hp_det_box_encode(int n, const float* d_boxes, const int32_t* d_match, const float* d_gt, int n_gt, float wx, float wy, float ww,
+                      float wh, float* d_out, void* stream);
+int hp_det_mask_targets(int n, const uint8_t* d_masks, int n_gt, int h, int w, const int32_t* d_match, const float* d_rois, int m,
+                        float* d_out, void* stream);
+int64_t hp_det_loss_workspace_bytes(int n_rows);
+int hp_loss_rpn(int n_anchors, int n_sampled, const int32_t* d_sampled, const float* d_objectness, const float* d_deltas,
+                const int32_t* d_labels, const float* d_targets, float* d_loss, float* d_grad_objectness, float* d_grad_deltas,
+                void* d_workspace, int64_t workspace_bytes, void* stream);
+int hp_loss_fastrcnn(int n, int n_classes, int ld, int ld_reg, const float* d_class_logits, const float* d_box_regression,
+                     const int32_t* d_labels, const float* d_targets, float* d_loss, float* d_grad_logits, float* d_grad_regression,
+                     void* d_workspace, int64_t workspace_bytes, void* stream);
+int hp_loss_mask(int n, int n_classes, int m, const float* d_mask_logits, const int32_t* d_labels, const float* d_targets, float* d_loss,
+                 float* d_grad_logits, void* d_workspace, int64_t workspace_bytes, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

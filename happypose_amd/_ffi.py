@@ -231,6 +231,10 @@ _PROTOS = {
     "hp_loss_fastrcnn": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_void_p,
                                    C.c_int64, C.c_void_p]),
     "hp_loss_mask": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_i32p, c_f32p, c_f32p, c_f32p, C.c_void_p, C.c_int64, C.c_void_p]),
+    "hp_pose_batch_select": (C.c_int, [C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_u8p, C.c_float, C.c_int, C.c_uint64, C.c_uint64, c_f32p,
+                                       c_f32p, c_i32p, c_u8p, c_f32p, c_f32p, c_i32p, c_i32p, C.c_void_p]),
+    "hp_batch_gather_chw": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_f32p, c_u8p, c_i32p, C.c_int, c_u8p, c_f32p, C.c_void_p]),
+    "hp_instance_masks": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, c_u8p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

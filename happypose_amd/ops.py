@@ -2337,3 +2337,131 @@ def loss_mask(mask_logits: torch.Tensor, labels: torch.Tensor, targets: torch.Te
         check(lib().hp_loss_mask(n, Cn, M, ptr(mask_logits), ptr(labels), ptr(targets), ptr(loss), ptr(grad), ptr(ws), nbytes,
                                  stream_ptr(dev)), "hp_loss_mask")
     return loss, grad
+
+
+# ---- batch assembly of the training data sets (csrc/batch_data.hip) ------------------------------------------------------------------
+def _dense(t, dtype, shape: tuple, what: str) -> torch.Tensor:
+    """A dense device tensor of ``dtype`` and ``shape`` (None: any size); a CPU tensor raises ValueError (no host implementation)."""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise ValueError(f"{what}: a tensor on the device is required (no CPU implementation)")
+    ok = t.dtype == dtype and t.dim() == len(shape) and all(s is None or int(d) == s for d, s in zip(t.shape, shape)) and t.is_contiguous()
+    if not ok:
+        want = "[" + ", ".join("*" if s is None else str(s) for s in shape) + "]"
+        raise ValueError(f"{what}: dense {want} {dtype} expected, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
+def _one_device(what: str, dev, *tensors) -> None:
+    for t in tensors:
+        if t is not None and t.device != dev:
+            raise ValueError(f"{what}: every tensor lives on one device, got {t.device} beside {dev}")
+
+
+def pose_batch_select(n_px: torch.Tensor, boxes: torch.Tensor, TWC: torch.Tensor, TWO: torch.Tensor, count=None,
+                      keep: Optional[torch.Tensor] = None, min_area: Optional[float] = None, first: bool = False, *, seed: int = 0,
+                      row_offset: int = 0):
+    """``hp_pose_batch_select``: one object per frame.  ``n_px [B, max_ids]``, ``boxes [B, max_ids, 4]`` int32 as ``seg_boxes``
+    returns them, ``TWC [B, 4, 4]``, ``TWO [B, max_ids, 4, 4]`` float32, ``count`` (a scalar or ``[B]``; default ``max_ids``),
+    ``keep [B, max_ids]`` bool / uint8 or None, ``min_area`` None or a number (``area >= min_area`` on the inclusive box without
+    + 1), ``first``: the first valid slot instead of the seeded one (``seed``, ``row_offset + b``).  Returns ``(chosen [B] int32,
+    valid [B] bool, bbox [B, 4] float32, TCO [B, 4, 4] float32, dst [B] int32, n_valid [1] int32)``, all on the device."""
+    n_px = _dense(n_px, torch.int32, (None, None), "pose_batch_select: n_px")
+    B, max_ids, dev = int(n_px.shape[0]), int(n_px.shape[1]), n_px.device
+    boxes = _dense(boxes, torch.int32, (B, max_ids, 4), "pose_batch_select: boxes")
+    TWC = _dense(TWC, torch.float32, (B, 4, 4), "pose_batch_select: TWC")
+    TWO = _dense(TWO, torch.float32, (B, max_ids, 4, 4), "pose_batch_select: TWO")
+    if keep is not None:
+        if isinstance(keep, torch.Tensor) and keep.dtype == torch.bool:
+            keep = keep.view(torch.uint8)
+        keep = _dense(keep, torch.uint8, (B, max_ids), "pose_batch_select: keep")
+    _one_device("pose_batch_select", dev, boxes, TWC, TWO, keep)
+    if not 1 <= max_ids <= SEG_BOXES_MAX_IDS:
+        raise ValueError(f"pose_batch_select: 1 .. {SEG_BOXES_MAX_IDS} ids per image, got {max_ids}")
+    if not (0 <= seed < 2 ** 64 and 0 <= row_offset < 2 ** 64):
+        raise ValueError("pose_batch_select: seed and row_offset are unsigned 64-bit integers")
+    area = -1.0 if min_area is None else float(min_area)
+    if not area >= 0.0 and min_area is not None:
+        raise ValueError(f"pose_batch_select: min_area is None or a number >= 0, got {min_area}")
+    chosen = torch.empty(B, dtype=torch.int32, device=dev)
+    valid = torch.empty(B, dtype=torch.uint8, device=dev)
+    bbox = torch.empty(B, 4, dtype=torch.float32, device=dev)
+    TCO = torch.empty(B, 4, 4, dtype=torch.float32, device=dev)
+    dst = torch.empty(B, dtype=torch.int32, device=dev)
+    n_valid = torch.zeros(1, dtype=torch.int32, device=dev)
+    if B:
+        cnt = _aug_param(max_ids if count is None else count, B, torch.int32, dev, "count")
+        with torch.cuda.device(dev):
+            check(lib().hp_pose_batch_select(B, max_ids, ptr(n_px), ptr(boxes), ptr(cnt), ptr(keep), C.c_float(area), int(bool(first)), seed,
+                                             row_offset, ptr(TWC), ptr(TWO), ptr(chosen), ptr(valid), ptr(bbox), ptr(TCO), ptr(dst),
+                                             ptr(n_valid), stream_ptr(dev)), "hp_pose_batch_select")
+    return chosen, valid.view(torch.bool), bbox, TCO, dst, n_valid
+
+
+def batch_gather_chw(rgb: torch.Tensor, valid: torch.Tensor, dst: torch.Tensor, n_out: Optional[int] = None,
+                     depth: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_depth: Optional[torch.Tensor] = None):
+    """``hp_batch_gather_chw``: ``rgb [B, H, W, 3]`` uint8 -> ``[n_out, 3, H, W]``, frame ``b`` with ``valid[b]`` to row ``dst[b]``
+    (``valid [B]`` bool / uint8 and ``dst [B]`` int32 as ``pose_batch_select`` returns them); with ``depth [B, H, W]`` float32 also
+    ``[n_out, H, W]``, bits copied.  ``n_out`` is the number of output rows (or pass ``out`` / ``out_depth``, which may be larger
+    than the number of valid frames: the rows no frame names are left as they are).  Returns ``(rgbs, depths or None)``."""
+    rgb = _aug_frames(rgb, "batch_gather_chw: rgb", torch.uint8, True)
+    B, h, w, dev = int(rgb.shape[0]), int(rgb.shape[1]), int(rgb.shape[2]), rgb.device
+    if isinstance(valid, torch.Tensor) and valid.dtype == torch.bool:
+        valid = valid.view(torch.uint8)
+    valid = _dense(valid, torch.uint8, (B,), "batch_gather_chw: valid")
+    dst = _dense(dst, torch.int32, (B,), "batch_gather_chw: dst")
+    if depth is not None:
+        depth = _dense(depth, torch.float32, (B, h, w), "batch_gather_chw: depth")
+    elif out_depth is not None:
+        raise ValueError("batch_gather_chw: out_depth without depth")
+    if n_out is None:
+        if out is None:
+            raise ValueError("batch_gather_chw: n_out or out is required (the number of valid frames lives on the device)")
+        n_out = int(out.shape[0])
+    if n_out < 0:
+        raise ValueError(f"batch_gather_chw: n_out = {n_out}")
+    if out is None:
+        out = torch.empty(n_out, 3, h, w, dtype=torch.uint8, device=dev)
+    out = _dense(out, torch.uint8, (n_out, 3, h, w), "batch_gather_chw: out")
+    if depth is not None:
+        if out_depth is None:
+            out_depth = torch.empty(n_out, h, w, dtype=torch.float32, device=dev)
+        out_depth = _dense(out_depth, torch.float32, (n_out, h, w), "batch_gather_chw: out_depth")
+    _one_device("batch_gather_chw", dev, valid, dst, depth, out, out_depth)
+    if B and n_out:
+        with torch.cuda.device(dev):
+            check(lib().hp_batch_gather_chw(B, h, w, ptr(rgb), ptr(depth), ptr(valid), ptr(dst), n_out, ptr(out), ptr(out_depth),
+                                            stream_ptr(dev)), "hp_batch_gather_chw")
+    return out, out_depth
+
+
+def instance_masks(segmentation: torch.Tensor, ids, slot_row, G: int, count=None, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_instance_masks``: ``masks [G, H, W]`` uint8, ``masks[slot_row[b, k]] = (segmentation[b] == ids[b, k])`` for the slots
+    with ``0 <= slot_row[b, k] < G`` (distinct rows).  ``segmentation [B, H, W]`` int32; ``ids`` and ``slot_row`` ``[B, max_ids]``
+    (arrays, or int32 device tensors), ``count`` a scalar or ``[B]`` (default ``max_ids``).  Rows are written completely."""
+    seg = _aug_frames(segmentation, "instance_masks: segmentation", torch.int32, False)
+    B, h, w, dev = int(seg.shape[0]), int(seg.shape[1]), int(seg.shape[2]), seg.device
+    tables = []
+    for name, t in (("ids", ids), ("slot_row", slot_row)):
+        if not (isinstance(t, torch.Tensor) and t.is_cuda):
+            a = np.asarray(t.cpu() if isinstance(t, torch.Tensor) else t)
+            if a.ndim != 2 or a.shape[0] != B or a.dtype.kind not in "iu" or (a.size and (a.min() < -2 ** 31 or a.max() >= 2 ** 31)):
+                raise ValueError(f"instance_masks: {name} must be [B, max_ids] integers that fit int32")
+            t = torch.from_numpy(np.ascontiguousarray(a, np.int32)).to(dev)
+        tables.append(_dense(t, torch.int32, (B, None), f"instance_masks: {name}"))
+    table, rows = tables
+    max_ids = int(table.shape[1])
+    if rows.shape != table.shape or not 1 <= max_ids <= SEG_BOXES_MAX_IDS:
+        raise ValueError(f"instance_masks: ids and slot_row [B, max_ids] with 1 .. {SEG_BOXES_MAX_IDS} ids per image")
+    G = int(G)
+    if G < 0:
+        raise ValueError(f"instance_masks: G = {G}")
+    if out is None:
+        out = torch.empty(G, h, w, dtype=torch.uint8, device=dev)
+    out = _dense(out, torch.uint8, (G, h, w), "instance_masks: out")
+    _one_device("instance_masks", dev, table, rows, out)
+    if B and G:
+        cnt = _aug_param(max_ids if count is None else count, B, torch.int32, dev, "count")
+        with torch.cuda.device(dev):
+            check(lib().hp_instance_masks(B, h, w, ptr(seg), ptr(table), ptr(cnt), ptr(rows), max_ids, G, ptr(out), stream_ptr(dev)),
+                  "hp_instance_masks")
+    return out

@@ -1326,6 +1326,65 @@ int hp_loss_fastrcnn(int n, int n_classes, int ld, int ld_reg, const float* d_cl
 int hp_loss_mask(int n, int n_classes, int m, const float* d_mask_logits, const int32_t* d_labels, const float* d_targets, float* d_loss,
                  float* d_grad_logits, void* d_workspace, int64_t workspace_bytes, void* stream);
 
+/* ------------------------------------------------------------------------------------
+ * Batch assembly of the training data sets: the step between a scene observation and the trainers' steps -- the reference's
+ * PoseDataset.make_data_from_obs + collate_fn (toolbox/datasets/pose_dataset.py) and DetectionDataset.make_data_from_obs
+ * (cosypose/datasets/detection_dataset.py) -- on frames, id maps and box tables that already live on the device.
+ * csrc/batch_data.hip; the user-facing layer is happypose_amd/datasets.py.
+ *
+ * Integers and copied bits only, except the pose product of hp_pose_batch_select; no atomics, one writer per output element:
+ * results are bit-identical from run to run.  Counts and indices read from device memory (d_count, d_dst, d_slot_row) are checked
+ * against the tables they address: a value outside is clamped or skipped, never followed.  B == 0 returns HP_OK and launches
+ * nothing; a null pointer, max_ids outside 1 .. 256, B > 65535 (gather, masks), a side < 1 or more than 2^28 pixels per frame is
+ * HP_ERR_ARG before the GPU is touched.
+ *
+ * hp_pose_batch_select  one object per frame.  d_n_px [B][max_ids] and d_boxes [B][max_ids][4] int32 as hp_seg_boxes writes them
+ *                   (inclusive x1, y1, x2, y2), d_count [B] (clamped to 0 .. max_ids), d_keep [B][max_ids] uint8 or NULL (the host
+ *                   evaluates keep_labels_set into it), d_TWC [B][4][4], d_TWO [B][max_ids][4][4] float32, row-major.
+ *                   Slot k of frame b is VALID when
+ *                     n_px > 0                                   remove_invisible_objects and `unique_id in unique_ids_visible`
+ *                                                                (the reference's second condition, `np.all(obj.bbox_modal) >= 0`,
+ *                                                                compares a boolean with 0 and is always true as written; it is not
+ *                                                                "fixed" here: there is no such condition)
+ *                     (x2 - x1) (y2 - y1) >= min_area            when min_area >= 0 (negative: no such condition; NaN: HP_ERR_ARG):
+ *                                                                the reference's arithmetic on the INCLUSIVE box, without + 1, so a
+ *                                                                one-pixel object has area 0; the product is an integer, compared
+ *                                                                in double
+ *                     d_keep[b][k] != 0                          when d_keep is given.
+ *                   The chosen slot is the first valid one (first != 0: return_first_object) or the k-th valid one in slot order,
+ *                   k = mulhi32(x0, n_valid) = (x0 n_valid) >> 32, x0 = word 0 of Philox4x32-10 with key (seed lo, seed hi) and
+ *                   counter (row lo, row hi, 0, 0), row = row_offset + b in 64 bits -- the constants and the key layout of
+ *                   hp_pose_add_noise, so a frame's choice depends on (seed, row_offset + b) and its own table alone.  The
+ *                   reference's random.sample stream is not reproduced.
+ *                   d_chosen [B] int32 (-1: no valid slot), d_valid [B] uint8, d_bbox [B][4] float32 the chosen box,
+ *                   d_TCO [B][4][4] = inverse(TWC) @ TWO[chosen] with the RIGID inverse: Ti[i][k] = TWC[k][i] (k < 3),
+ *                   Ti[i][3] = -((TWC[0][i] t0 + TWC[1][i] t1) + TWC[2][i] t2), t = TWC[.][3];
+ *                   TCO[i][j] = ((Ti[i][0] B[0][j] + Ti[i][1] B[1][j]) + Ti[i][2] B[2][j]) + Ti[i][3] B[3][j] for i < 3, evaluated in
+ *                   double from the float32 inputs in this order and rounded once; row 3 is TWO's row 3, copied.  A frame without a
+ *                   valid slot has bbox and TCO 0.  d_dst [B] int32: the exclusive scan of d_valid, the row of frame b among the
+ *                   valid frames (defined for every b); d_n_valid [1] their number (0 when B == 0).
+ * hp_batch_gather_chw   the collate step.  d_rgb [B][h][w][3] uint8 -> d_out_rgb [n_out][3][h][w]: frame b goes to row d_dst[b]; a
+ *                   frame with d_valid[b] == 0 or a row outside 0 .. n_out - 1 is skipped, and rows no frame names keep what they
+ *                   held.  With d_depth [B][h][w] float32 (and d_out_depth [n_out][h][w]; both or neither) the depth follows in the
+ *                   same launch, bits copied (NaN, -0).  Loads and stores are 16-byte vectors on the 16-byte grid of each address,
+ *                   the interleaved-to-planar transposition goes through the LDS, and byte ranges that do not start or end on the
+ *                   grid (h w odd) are completed byte by byte by the lanes that own the straddling vectors.  The outputs must not
+ *                   alias the inputs.
+ * hp_instance_masks     the detector's targets.  d_segmentation [B][h][w] int32, d_ids [B][max_ids], d_count [B] as for
+ *                   hp_seg_boxes; d_slot_row [B][max_ids] int32: the output row of a kept slot, -1 (or any value outside
+ *                   0 .. G - 1) for a slot that is not kept; the rows of kept slots are distinct.  d_masks [G][h][w] uint8:
+ *                   masks[row] = (segmentation[b] == ids[b][slot]), 0 / 1.  A frame's id map is read once and all of its masks are
+ *                   written from it, 16 pixels per vector store.  Rows are written completely: the caller need not clear d_masks.
+ *                   G == 0 and frames without kept slots are legal.
+ * ---------------------------------------------------------------------------------- */
+int hp_pose_batch_select(int B, int max_ids, const int32_t* d_n_px, const int32_t* d_boxes, const int32_t* d_count, const uint8_t* d_keep,
+                         float min_area, int first, uint64_t seed, uint64_t row_offset, const float* d_TWC, const float* d_TWO,
+                         int32_t* d_chosen, uint8_t* d_valid, float* d_bbox, float* d_TCO, int32_t* d_dst, int32_t* d_n_valid, void* stream);
+int hp_batch_gather_chw(int B, int h, int w, const uint8_t* d_rgb, const float* d_depth, const uint8_t* d_valid, const int32_t* d_dst,
+                        int n_out, uint8_t* d_out_rgb, float* d_out_depth, void* stream);
+int hp_instance_masks(int B, int h, int w, const int32_t* d_segmentation, const int32_t* d_ids, const int32_t* d_count,
+                      const int32_t* d_slot_row, int max_ids, int G, uint8_t* d_masks, void* stream);
+
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop
 #endif

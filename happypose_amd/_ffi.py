@@ -235,6 +235,17 @@ _PROTOS = {
                                        c_f32p, c_i32p, c_u8p, c_f32p, c_f32p, c_i32p, c_i32p, C.c_void_p]),
     "hp_batch_gather_chw": (C.c_int, [C.c_int, C.c_int, C.c_int, c_u8p, c_f32p, c_u8p, c_i32p, C.c_int, c_u8p, c_f32p, C.c_void_p]),
     "hp_instance_masks": (C.c_int, [C.c_int, C.c_int, C.c_int, c_i32p, c_i32p, c_i32p, c_i32p, C.c_int, C.c_int, c_u8p, C.c_void_p]),
+    "hp_net_set_param_device": (C.c_int, [C.c_void_p, C.c_char_p, c_f32p, C.c_int64, C.c_void_p]),
+    "hp_net_get_param_device": (C.c_int, [C.c_void_p, C.c_char_p, c_f32p, C.c_int64, C.c_void_p]),
+    "hp_net_set_pooled_out":(C.c_int, [C.c_void_p, c_f32p]),
+    "hp_head_backward_ws_floats": (C.c_int64, [C.c_int, C.c_int, C.c_int]),
+    "hp_head_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, c_f32p, c_f32p, c_f32p, C.c_int, c_f32p, c_f32p,
+                                   c_f32p, c_f32p, C.c_int64, C.c_void_p]),
+    "hp_fc_backward": (C.c_int, [C.c_int, C.c_int, C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, c_f32p, C.c_void_p]),
+    "hp_grad_sq_norm_ws_floats": (C.c_int64, [C.c_int64]),
+    "hp_grad_sq_norm": (C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p, C.c_int64, C.c_void_p]),
+    "hp_adamw_step": (C.c_int, [C.c_int64, c_f32p, c_f32p, c_f32p, c_f32p, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double,
+                                C.c_int64, C.c_int, c_f32p, c_f32p, C.c_void_p]),
 }
 
 EXPORTED_SYMBOLS = tuple(_PROTOS)

@@ -19,7 +19,7 @@ LIB_DIR = PKG / "lib"
 LIB = LIB_DIR / "libhappypose_amd.so"
 TORCH_LIB = LIB_DIR / "libhappypose_amd_torch.so"
 OBJ_DIR = PKG / "build_obj"
-SOURCES = ["api.cpp", "debug.cpp", "net.cpp", "raster.hip", "geometry.hip", "crop.hip", "conv.hip", "conv_patch.hip", "conv_wino.hip", "conv_split.hip", "conv_pp.hip", "conv_igemm_split.hip", "conv_stem_split.hip", "conv_stem7.hip", "conv_f16.hip", "pool_head.hip", "icp.hip", "teaser.hip", "mbconv.hip", "mbconv_front.hip", "probe.hip", "detect.hip", "multiview.hip", "pose_errors.hip", "scene.hip", "vsd.hip", "det_eval.hip", "mesh_sample.hip", "pose_losses.hip", "augment.hip", "resize.hip", "train_hyp.hip", "det_losses.hip", "batch_data.hip"]
+SOURCES = ["api.cpp", "debug.cpp", "net.cpp", "raster.hip", "geometry.hip", "crop.hip", "conv.hip", "conv_patch.hip", "conv_wino.hip", "conv_split.hip", "conv_pp.hip", "conv_igemm_split.hip", "conv_stem_split.hip", "conv_stem7.hip", "conv_f16.hip", "pool_head.hip", "icp.hip", "teaser.hip", "mbconv.hip", "mbconv_front.hip", "probe.hip", "detect.hip", "multiview.hip", "pose_errors.hip", "scene.hip", "vsd.hip", "det_eval.hip", "mesh_sample.hip", "pose_losses.hip", "augment.hip", "resize.hip", "train_hyp.hip", "det_losses.hip", "batch_data.hip", "head_train.hip"]
 # -fno-slp-vectorize: the SLP vectoriser turns adjacent scalar fp32 operations into packed-fp32 instructions (v_pk_fma_f32 /
 # v_pk_mul_f32 / v_pk_add_f32 with op_sel operand swizzles).  On gfx950 / ROCm 7.2 those intermittently returned WRONG
 # values when the SIMD co-executed another queue's MFMA stream (two-lane steps: the rasteriser's set-up planes beside the

@@ -106,6 +106,7 @@ struct Net {
   std::vector<DevBuf> bufs;
   DevBuf fc_w, fc_b, pose_w, pose_b, logit_w, logit_b;
   DevBuf head_ws;  // fc path of the head: 2 x [max_batch][512] floats
+  float* pooled_out = nullptr;  // hp_net_set_pooled_out: where a forward also leaves the fc's input (head training)
   int pose_dim = 0, n_logits = 0;
   int feat_H = 0, feat_W = 0;
   struct FeatureMap { int buf, H, W, C; };
@@ -731,6 +732,56 @@ extern "C" int hp_net_set_param(hp_net* net, const char* name, const float* h_da
   return HP_OK;
 }
 
+// The tensors csrc/pool_head.hip reads as plain fp32 are stored as they were handed over: a copy on `stream` replaces one in a
+// finalised network (no re-planning: the launch plan holds the buffers' addresses, which do not change).  Everything else was
+// folded (BN into conv weights) or packed (tile order, fp16 splits, Winograd transforms) at finalise and is refused.
+static int head_param(hp_net* net, const char* name, int64_t numel, const char* what, DevBuf** buf) {
+  HP_REQUIRE(net && name, std::string(what) + ": bad argument");
+  HP_REQUIRE(net->finalized, std::string(what) + ": network not finalized (hp_net_set_param takes host data before that)");
+  const std::string k(name);
+  const int64_t C = net->n_features;
+  DevBuf* dst = nullptr;
+  int64_t want = 0;
+  if (k == "pose_fc.weight") { dst = &net->pose_w; want = net->pose_dim * C; }
+  else if (k == "pose_fc.bias") { dst = &net->pose_b; want = net->pose_dim; }
+  else if (k == "views_logits_head.weight") { dst = &net->logit_w; want = net->n_logits * C; }
+  else if (k == "views_logits_head.bias") { dst = &net->logit_b; want = net->n_logits; }
+  else if (k == "backbone.fc.weight") { dst = &net->fc_w; want = 512 * 512; }
+  else if (k == "backbone.fc.bias") { dst = &net->fc_b; want = 512; }
+  else
+    return fail(HP_ERR_ARG, std::string(what) + ": '" + k + "' is folded or packed at finalise; only the head tensors (pose_fc, "
+                            "views_logits_head, backbone.fc) are kept as plain fp32 in a finalised network");
+  HP_REQUIRE(dst->p && want > 0, std::string(what) + ": the network has no '" + k + "'");
+  HP_REQUIRE(numel == want, std::string(what) + ": '" + k + "' has " + std::to_string(want) + " elements, got " + std::to_string(numel));
+  *buf = dst;
+  return HP_OK;
+}
+
+extern "C" int hp_net_set_param_device(hp_net* net, const char* name, const float* d_data, int64_t numel, void* stream) {
+  HP_REQUIRE(d_data, "hp_net_set_param_device: null data");
+  DevBuf* buf = nullptr;
+  int rc = head_param(net, name, numel, "hp_net_set_param_device", &buf);
+  if (rc) return rc;
+  HP_CHECK_HIP(hipMemcpyAsync(buf->p, d_data, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return HP_OK;
+}
+
+extern "C" int hp_net_get_param_device(hp_net* net, const char* name, float* d_data, int64_t numel, void* stream) {
+  HP_REQUIRE(d_data, "hp_net_get_param_device: null data");
+  DevBuf* buf = nullptr;
+  int rc = head_param(net, name, numel, "hp_net_get_param_device", &buf);
+  if (rc) return rc;
+  HP_CHECK_HIP(hipMemcpyAsync(d_data, buf->p, (size_t)numel * 4, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+  return HP_OK;
+}
+
+extern "C" int hp_net_set_pooled_out(hp_net* net, float* d_pooled) {
+  HP_REQUIRE(net && net->finalized, "hp_net_set_pooled_out: network not finalized");
+  HP_REQUIRE(!d_pooled || net->fc_w.p, "hp_net_set_pooled_out: the network has no fc in front of its heads");
+  net->pooled_out = d_pooled;
+  return HP_OK;
+}
+
 extern "C" int hp_net_set_precision(hp_net* net, int precision) {
   HP_REQUIRE(net, "hp_net_set_precision: null net");
   HP_REQUIRE(!net->finalized, "hp_net_set_precision: network already finalized");
@@ -1194,6 +1245,8 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       h.pose_out = d_pose; h.logit_out = d_logits; h.features = d_features;
       h.ws_pool = (float*)net->head_ws.p; h.ws_fc = h.ws_pool ? h.ws_pool + (size_t)net->max_batch * 512 : nullptr;
       if ((rc = launch_head(h, batch, stream))) return rc;
+      if (net->pooled_out && h.ws_pool)
+        HP_CHECK_HIP(hipMemcpyAsync(net->pooled_out + (size_t)b0 * 512, h.ws_pool, (size_t)batch * 512 * 4, hipMemcpyDeviceToDevice, stream));
       written = false;
       note(oi, HP_PATH_HEAD, false);
     }

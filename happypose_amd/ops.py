@@ -487,6 +487,12 @@ class Net:
     _sibling: Optional["Net"] = None
     _on_sibling = False
     _host_params = None  # fp16 plan: the parameters on the host, what the sibling is built from
+    # fp16 plan: the head tensors replaced on the device since (set_param_device) -- ``_host_params`` is stale for them, so a
+    # sibling built later is given these on top
+    _device_params: Optional[Dict[str, torch.Tensor]] = None
+
+    HEAD_PARAMS = ("pose_fc.weight", "pose_fc.bias", "views_logits_head.weight", "views_logits_head.bias", "backbone.fc.weight",
+                   "backbone.fc.bias")
 
     def __init__(self, arch: str, n_inputs: int, state_dict: Dict[str, "np.ndarray | torch.Tensor"],
                  max_batch: int = 128, device="cuda", h: int = 240, w: int = 320, precision: str = "f32"):
@@ -550,8 +556,52 @@ class Net:
             if self.profiling:
                 check(lib().hp_net_set_profiling(sib.handle, 1), "hp_net_set_profiling")
                 sib.profiling = True
+            for name, t in (self._device_params or {}).items():  # heads trained since this plan was built
+                sib.set_param_device(name, t)
             self._sibling = sib
         return self._sibling
+
+    def head_param_shapes(self) -> Dict[str, Tuple[int, ...]]:
+        """The head tensors this network has (:attr:`HEAD_PARAMS`), by the reference's names, with their shapes."""
+        out: Dict[str, Tuple[int, ...]] = {}
+        if self.arch == "vanilla_resnet34":
+            out["backbone.fc.weight"], out["backbone.fc.bias"] = (512, 512), (512,)
+        if self.pose_dim:
+            out["pose_fc.weight"], out["pose_fc.bias"] = (self.pose_dim, self.n_features), (self.pose_dim,)
+        if self.n_logits:
+            out["views_logits_head.weight"], out["views_logits_head.bias"] = (self.n_logits, self.n_features), (self.n_logits,)
+        return out
+
+    def get_param_device(self, name: str, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """``hp_net_get_param_device``: a head tensor as the network holds it now, copied on the current stream (the plan the
+        fp16 front was built as; its sibling holds the same heads)."""
+        shape = self.head_param_shapes().get(name)
+        if shape is None:
+            raise KeyError(f"{name!r} is not a head tensor of this network ({sorted(self.head_param_shapes())})")
+        out = torch.empty(shape, dtype=torch.float32, device=self.device) if out is None else out
+        assert out.dtype == torch.float32 and out.is_contiguous() and out.numel() == int(np.prod(shape))
+        with torch.cuda.device(self.device):
+            check(lib().hp_net_get_param_device(self.handle, name.encode(), ptr(out), out.numel(), stream_ptr(self.device)),
+                  f"hp_net_get_param_device({name})")
+        return out
+
+    def set_param_device(self, name: str, value: torch.Tensor) -> None:
+        """``hp_net_set_param_device``: replace a head tensor (:attr:`HEAD_PARAMS`) of the finalised network by a float32 tensor
+        on its device, with a copy on the current stream -- no host round trip, no re-planning, captured graphs stay valid.  Any
+        other name raises (conv and BN weights are folded or packed at finalise).  An fp16 plan hands the tensor to its fp32
+        sibling too: at once when the sibling exists, else when the guard builds it -- ``value`` is kept (not copied) for
+        that, so it must then still hold what was set (a trainer's master copy does)."""
+        assert isinstance(value, torch.Tensor) and value.dtype == torch.float32 and value.is_contiguous(), \
+            "set_param_device: a contiguous float32 tensor"
+        with torch.cuda.device(self.device):
+            check(lib().hp_net_set_param_device(self.handle, name.encode(), ptr(value), value.numel(), stream_ptr(self.device)),
+                  f"hp_net_set_param_device({name})")
+        if self.precision == "f16":
+            if self._device_params is None:
+                self._device_params = {}
+            self._device_params[name] = value
+            if self._sibling is not None:
+                self._sibling.set_param_device(name, value)
 
     def _switch(self, on: bool) -> None:
         """Send every later call to the fp32 sibling (``on``) or back to the fp16 plan; a transition changes the launch
@@ -581,10 +631,19 @@ class Net:
             return torch.zeros((batch, self.h, self.w, self.c16), dtype=torch.float16, device=self.device)
         return torch.zeros((batch, self.h, self.w, self.c_pad), dtype=torch.float32, device=self.device)
 
-    def forward(self, x: torch.Tensor, want_pose=True, want_logits=False, want_features=False):
+    def forward(self, x: torch.Tensor, want_pose=True, want_logits=False, want_features=False, pooled_out: Optional[torch.Tensor] = None):
+        """``pooled_out [b, 512]`` (networks with the fc, ``arch == "vanilla_resnet34"``): also receives the fc's input, the
+        spatial mean (``hp_net_set_pooled_out`` around this call)."""
         if self._on_sibling:
             assert x.dtype == torch.float32, "this fp16 network runs on its fp32 sibling now: take the input from new_input()"
-            return self._sibling.forward(x, want_pose=want_pose, want_logits=want_logits, want_features=want_features)
+            return self._sibling.forward(x, want_pose=want_pose, want_logits=want_logits, want_features=want_features, pooled_out=pooled_out)
+        if pooled_out is not None:
+            assert pooled_out.shape == (x.shape[0], 512) and pooled_out.dtype == torch.float32 and pooled_out.is_contiguous()
+            check(lib().hp_net_set_pooled_out(self.handle, ptr(pooled_out)), "hp_net_set_pooled_out")
+            try:
+                return self.forward(x, want_pose=want_pose, want_logits=want_logits, want_features=want_features)
+            finally:
+                check(lib().hp_net_set_pooled_out(self.handle, None), "hp_net_set_pooled_out")
         b = x.shape[0]
         f = dict(dtype=torch.float32, device=self.device)
         if x.dtype == torch.float16:
@@ -1295,6 +1354,110 @@ def tco_init_from_boxes(boxes: torch.Tensor, K: torch.Tensor, z_range=(1.0, 1.0)
                                            C.c_float(z_range[0]), C.c_float(z_range[1]), ptr(out), stream_ptr(dev)),
               "hp_tco_init_from_boxes")
     return out
+
+
+# ---- head training (csrc/head_train.hip) -----------------------------------------------------------------------------------------
+def _f32_in(what: str, name: str, t: Optional[torch.Tensor], shape) -> None:
+    if t is not None:
+        assert t.dtype == torch.float32 and t.is_contiguous() and tuple(t.shape) == tuple(shape), \
+            f"{what}: {name} must be contiguous float32 {list(shape)}, got {t.dtype} {list(t.shape)}"
+
+
+def head_backward(feat: torch.Tensor, d_pose: torch.Tensor, W: Optional[torch.Tensor] = None, *, d_logits: Optional[torch.Tensor] = None,
+                  n_logits: int = 0, w: Optional[torch.Tensor] = None, dW: Optional[torch.Tensor] = None,
+                  db: Optional[torch.Tensor] = None, accumulate: bool = False, return_d_feat: bool = False):
+    """``hp_head_backward``: ``feat [B, C]``, ``d_pose [B, pose_dim]`` and ``d_logits [B, n_logits]`` (None: zeros; ``n_logits``
+    then gives the width) -> ``dW [O, C]``, ``db [O]`` with ``O = pose_dim + n_logits``, the pose rows first; optional row
+    weights ``w [B]``.  ``dW`` / ``db`` given: written in place, added to with ``accumulate``.  ``return_d_feat``: also
+    ``d_feat [B, C] = (w d_out) @ W`` -- ``W [O, C]`` is needed for it alone.  Bit-identical from run to run (the header states the
+    order of the sums)."""
+    dev = _on_device("head_backward", feat=feat, d_pose=d_pose, d_logits=d_logits, w=w, W=W, dW=dW, db=db)
+    assert feat.dim() == 2 and d_pose.dim() == 2, "head_backward: feat [B, C], d_pose [B, pose_dim]"
+    B, Cf = feat.shape
+    pose_dim = d_pose.shape[1]
+    if d_logits is not None:
+        assert d_logits.dim() == 2, "head_backward: d_logits [B, n_logits]"
+        n_logits = d_logits.shape[1]
+    O = pose_dim + n_logits
+    assert 1 <= O <= 32, "head_backward: pose_dim + n_logits must be 1 .. 32"
+    assert not accumulate or (dW is not None and db is not None), "head_backward: accumulate adds to given dW / db"
+    assert not return_d_feat or W is not None, "head_backward: d_feat needs the head matrix W [O, C]"
+    _f32_in("head_backward", "feat", feat, (B, Cf))
+    _f32_in("head_backward", "d_pose", d_pose, (B, pose_dim))
+    _f32_in("head_backward", "d_logits", d_logits, (B, n_logits))
+    _f32_in("head_backward", "w", w, (B,))
+    _f32_in("head_backward", "W", W, (O, Cf))
+    f = dict(dtype=torch.float32, device=dev)
+    dW = torch.empty((O, Cf), **f) if dW is None else dW
+    db = torch.empty((O,), **f) if db is None else db
+    _f32_in("head_backward", "dW", dW, (O, Cf))
+    _f32_in("head_backward", "db", db, (O,))
+    d_feat = torch.empty((B, Cf), **f) if return_d_feat else None
+    n_ws = int(lib().hp_head_backward_ws_floats(B, Cf, O))
+    ws = torch.empty((max(n_ws, 1),), **f)
+    with torch.cuda.device(dev):
+        check(lib().hp_head_backward(B, Cf, pose_dim, n_logits, ptr(feat), ptr(d_pose), ptr(d_logits), ptr(w), ptr(W), int(bool(accumulate)),
+                                     ptr(dW), ptr(db), ptr(d_feat), ptr(ws), n_ws, stream_ptr(dev)), "hp_head_backward")
+    return (dW, db, d_feat) if return_d_feat else (dW, db)
+
+
+def fc_backward(d_out: torch.Tensor, x: torch.Tensor, *, dW: Optional[torch.Tensor] = None, db: Optional[torch.Tensor] = None,
+                accumulate: bool = False):
+    """``hp_fc_backward``: ``d_out [B, O]`` (the ``d_feat`` of :func:`head_backward`), the layer's input ``x [B, C]`` ->
+    ``dW [O, C] = d_out^T x`` and ``db [O]``, the sum over the rows one chain in index order."""
+    dev = _on_device("fc_backward", d_out=d_out, x=x, dW=dW, db=db)
+    assert d_out.dim() == 2 and x.dim() == 2 and d_out.shape[0] == x.shape[0], "fc_backward: d_out [B, O], x [B, C]"
+    (B, O), Cx = d_out.shape, x.shape[1]
+    assert O >= 1 and Cx >= 1, "fc_backward: empty layer"
+    assert not accumulate or (dW is not None and db is not None), "fc_backward: accumulate adds to given dW / db"
+    _f32_in("fc_backward", "d_out", d_out, (B, O))
+    _f32_in("fc_backward", "x", x, (B, Cx))
+    f = dict(dtype=torch.float32, device=dev)
+    dW = torch.empty((O, Cx), **f) if dW is None else dW
+    db = torch.empty((O,), **f) if db is None else db
+    _f32_in("fc_backward", "dW", dW, (O, Cx))
+    _f32_in("fc_backward", "db", db, (O,))
+    with torch.cuda.device(dev):
+        check(lib().hp_fc_backward(B, O, Cx, ptr(d_out), ptr(x), int(bool(accumulate)), ptr(dW), ptr(db), stream_ptr(dev)), "hp_fc_backward")
+    return dW, db
+
+
+def grad_sq_norm(g: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """``hp_grad_sq_norm``: the sum of squares of a flat float32 buffer as a device scalar ``[1]`` (fixed-order two-level
+    reduction, bit-identical from run to run).  Its square root is ``clip_grad_norm_``'s total norm."""
+    dev = _on_device("grad_sq_norm", g=g, out=out)
+    assert g.dim() == 1 and g.dtype == torch.float32 and g.is_contiguous(), "grad_sq_norm: a flat contiguous float32 buffer"
+    n = g.shape[0]
+    assert n < 2 ** 31, "grad_sq_norm: at most 2^31 - 1 elements"
+    out = torch.empty((1,), dtype=torch.float32, device=dev) if out is None else out
+    _f32_in("grad_sq_norm", "out", out, (1,))
+    n_ws = int(lib().hp_grad_sq_norm_ws_floats(n))
+    ws = torch.empty((max(n_ws, 1),), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_grad_sq_norm(n, ptr(g), ptr(out), ptr(ws), n_ws, stream_ptr(dev)), "hp_grad_sq_norm")
+    return out
+
+
+def adamw_step(p: torch.Tensor, g: torch.Tensor, m: torch.Tensor, v: torch.Tensor, *, lr: float, betas=(0.9, 0.999), eps: float = 1e-8,
+               weight_decay: float = 0.0, step: int, decoupled: bool = False, sq_norm: Optional[torch.Tensor] = None,
+               max_norm: Optional[torch.Tensor] = None) -> None:
+    """``hp_adamw_step``: one launch over the flat float32 buffers ``p``, ``g``, ``m``, ``v [N]``; ``p``, ``m``, ``v`` are updated
+    in place in the operation order of torch's ``_single_tensor_adam`` (``decoupled``: ``AdamW``; else ``Adam`` with L2).
+    ``sq_norm`` (from :func:`grad_sq_norm`) and ``max_norm``, device scalars ``[1]``, both or neither: the gradient is clipped by
+    ``min(1, max_norm / (sqrt(sq_norm) + 1e-6))`` inside the launch.  ``step`` counts from 1."""
+    dev = _on_device("adamw_step", p=p, g=g, m=m, v=v, sq_norm=sq_norm, max_norm=max_norm)
+    assert p.dim() == 1 and p.shape[0] < 2 ** 31, "adamw_step: flat buffers of at most 2^31 - 1 elements"
+    n = p.shape[0]
+    for name, t in (("p", p), ("g", g), ("m", m), ("v", v)):
+        _f32_in("adamw_step", name, t, (n,))
+    _f32_in("adamw_step", "sq_norm", sq_norm, (1,))
+    _f32_in("adamw_step", "max_norm", max_norm, (1,))
+    assert (sq_norm is None) == (max_norm is None), "adamw_step: sq_norm and max_norm come together"
+    assert int(step) >= 1, "adamw_step: step counts from 1"
+    with torch.cuda.device(dev):
+        check(lib().hp_adamw_step(n, ptr(p), ptr(g), ptr(m), ptr(v), float(lr), float(betas[0]), float(betas[1]), float(eps),
+                                  float(weight_decay), int(step), int(bool(decoupled)), ptr(sq_norm), ptr(max_norm), stream_ptr(dev)),
+              "hp_adamw_step")
 
 
 # --------------------------------------------------------------------------------------------------------------- scenes (scene.hip)

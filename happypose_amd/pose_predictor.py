@@ -204,7 +204,7 @@ class _RenderAndCompare:
 
     def _one_pass(self, images, K, im_ids, obj_ids, TCO_in, *, n_img_channels, multiview_type, normalize,
                   render_normals, render_depth, depth_mode, want_pose, want_logits, remove_TCO_rendering=False,
-                  scene_lights=False):
+                  scene_lights=False, want_features=False):
         b = TCO_in.shape[0]
         prep = ops.pose_prep(self.store, TCO_in, K, im_ids, obj_ids, tuple(images.shape[-2:]),
                              self.render_size, multiview_type=multiview_type, normalize=normalize,
@@ -237,6 +237,15 @@ class _RenderAndCompare:
                               chan0=n_img_channels, depth_norm_z=z, depth_norm_mode=depth_mode, msaa=self.renderer.msaa,
                               aniso=self.renderer.aniso, **lights)
         render_time = time.time() - t0
+        if want_features:
+            # head training (happypose_amd.training.HeadTrainer): the vector the linear heads read and, where an fc sits in
+            # front of them, the fc's input too -- same launches, two more outputs
+            pooled = (torch.empty((b, 512), dtype=torch.float32, device=self.device)
+                      if self.backbone.arch == "vanilla_resnet34" else None)
+            pose, logits, prep["features"] = self.backbone.forward(x, want_pose=want_pose, want_logits=want_logits, want_features=True,
+                                                                   pooled_out=pooled)
+            prep["pooled"] = pooled
+            return prep, x, pose, logits, render_time
         pose, logits, _ = self.backbone.forward(x, want_pose=want_pose, want_logits=want_logits)
         return prep, x, pose, logits, render_time
 
@@ -301,7 +310,10 @@ class PosePredictor(_RenderAndCompare):
     @torch.no_grad()
     def forward(self, images: torch.Tensor, K: torch.Tensor, labels: Sequence[str], TCO: torch.Tensor,
                 n_iterations: int = 1, random_ambient_light: bool = False,
-                im_ids: Optional[torch.Tensor] = None) -> Dict[str, PosePredictorOutput]:
+                im_ids: Optional[torch.Tensor] = None, return_features: bool = False) -> Dict[str, PosePredictorOutput]:
+        """``return_features`` (off: every output as before): each iteration's ``network_outputs`` also carries ``"features"``
+        ``[B, n_features]``, the vector the linear heads read, and on the fc path ``"pooled"`` ``[B, 512]``, the fc's input.
+        Such a call runs eagerly (no graph replay)."""
         assert not random_ambient_light, "random_ambient_light is a training-time augmentation"
         bsz = len(labels)
         assert TCO.shape == (bsz, 4, 4)
@@ -310,16 +322,19 @@ class PosePredictor(_RenderAndCompare):
         per_hyp = im_ids is None
         im_ids, obj_ids = self._ids(images, K, labels, im_ids)
         TCO_input = TCO.to(self.device, torch.float32)
-        recs = self._run_refine((n_iterations,), [images, K, im_ids, obj_ids, TCO_input],
-                                lambda *t: self._refine_device(*t, n_iterations=n_iterations))
+        if return_features:
+            recs = self._refine_device(images, K, im_ids, obj_ids, TCO_input, n_iterations=n_iterations, return_features=True)
+        else:
+            recs = self._run_refine((n_iterations,), [images, K, im_ids, obj_ids, TCO_input],
+                                    lambda *t: self._refine_device(*t, n_iterations=n_iterations))
         return self._build_outputs(recs, list(labels), K, per_hyp, im_ids)
 
-    def _refine_device(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int):
+    def _refine_device(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int, return_features: bool = False):
         """The device program of ``forward``: only launches on tensors (capturable as a hipGraph).  One record per
         iteration."""
-        return list(self._refine_iter(images, K, im_ids, obj_ids, TCO_input, n_iterations=n_iterations))
+        return list(self._refine_iter(images, K, im_ids, obj_ids, TCO_input, n_iterations=n_iterations, return_features=return_features))
 
-    def _refine_iter(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int):
+    def _refine_iter(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int, return_features: bool = False):
         """``_refine_device`` as a generator: yields an iteration's record once its launches are enqueued, so that
         ``TwoLanePredictor`` can enqueue its lanes' chains alternately (a lane whose whole chain is enqueued only after
         the other's starts milliseconds late whenever the caller synchronises between calls, as the estimators do)."""
@@ -329,7 +344,7 @@ class PosePredictor(_RenderAndCompare):
                 multiview_type=self.multiview_type, normalize=True, render_normals=self.render_normals,
                 render_depth=self.render_depth, depth_mode=self._depth_mode,
                 want_pose=self.predict_pose_update, want_logits=self.predict_rendered_views_logits,
-                remove_TCO_rendering=self._skip_tco, scene_lights=not self.render_normals)
+                remove_TCO_rendering=self._skip_tco, scene_lights=not self.render_normals, want_features=return_features)
             TCO_norm = prep["TCO"]
             if self.predict_pose_update:
                 TCO_output = ops.pose_update(TCO_norm, prep["K_crop_main"].contiguous() if self._skip_tco else prep["K_crop"], pose,
@@ -340,7 +355,8 @@ class PosePredictor(_RenderAndCompare):
             yield dict(TCO_input=TCO_norm, TCO_output=TCO_output, TCV_O=prep["TCV_O"], tCR=prep["tCR"],
                        KV_crop=prep["K_crop"], K_crop=prep["K_crop_main"] if self._skip_tco else None,
                        boxes_rend=prep["boxes_rend"], boxes_crop=prep["boxes_crop"],
-                       pose=pose, logits=logits, images_crop=images_crop, renders=renders, render_time=render_time)
+                       pose=pose, logits=logits, images_crop=images_crop, renders=renders, render_time=render_time,
+                       features=prep.get("features"), pooled=prep.get("pooled"))
             TCO_input = TCO_output
 
     def _build_outputs(self, recs, labels, K, per_hyp, im_ids) -> Dict[str, PosePredictorOutput]:
@@ -352,6 +368,9 @@ class PosePredictor(_RenderAndCompare):
                 net_out["pose"] = r["pose"]
             if r["logits"] is not None:
                 net_out["renderings_logits"] = r["logits"]
+            for key in ("features", "pooled"):
+                if r.get(key) is not None:
+                    net_out[key] = r[key]
             outputs[f"iteration={n + 1}"] = PosePredictorOutput(
                 renders=r["renders"], images_crop=r["images_crop"], TCO_input=r["TCO_input"], TCO_output=r["TCO_output"],
                 TCV_O_input=r["TCV_O"], tCR=r["tCR"], labels=labels, K=Kb,
@@ -407,7 +426,9 @@ class CosyPosePosePredictor(_RenderAndCompare):
 
     @torch.no_grad()
     def forward(self, images: torch.Tensor, K: torch.Tensor, labels: Sequence[str], TCO: torch.Tensor,
-                n_iterations: int = 1, im_ids: Optional[torch.Tensor] = None) -> Dict[str, PosePredictorOutput]:
+                n_iterations: int = 1, im_ids: Optional[torch.Tensor] = None,
+                return_features: bool = False) -> Dict[str, PosePredictorOutput]:
+        """``return_features``: see ``PosePredictor.forward``."""
         bsz = len(labels)
         assert images.dim() == 4 and images.shape[1] >= 3
         assert K.dim() == 3 and K.shape[1:] == (3, 3)
@@ -415,24 +436,29 @@ class CosyPosePosePredictor(_RenderAndCompare):
         per_hyp = im_ids is None
         im_ids, obj_ids = self._ids(images, K, labels, im_ids)
         TCO_input = TCO.to(self.device, torch.float32)
-        recs = self._run_refine((n_iterations,), [images, K, im_ids, obj_ids, TCO_input],
-                                lambda *t: self._refine_device(*t, n_iterations=n_iterations))
+        if return_features:
+            recs = self._refine_device(images, K, im_ids, obj_ids, TCO_input, n_iterations=n_iterations, return_features=True)
+        else:
+            recs = self._run_refine((n_iterations,), [images, K, im_ids, obj_ids, TCO_input],
+                                    lambda *t: self._refine_device(*t, n_iterations=n_iterations))
         return self._build_outputs(recs, list(labels), K, per_hyp, im_ids)
 
-    def _refine_device(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int):
+    def _refine_device(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int, return_features: bool = False):
         """The device program of ``forward`` (see ``PosePredictor._refine_device``)."""
-        return list(self._refine_iter(images, K, im_ids, obj_ids, TCO_input, n_iterations=n_iterations))
+        return list(self._refine_iter(images, K, im_ids, obj_ids, TCO_input, n_iterations=n_iterations, return_features=return_features))
 
-    def _refine_iter(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int):
+    def _refine_iter(self, images, K, im_ids, obj_ids, TCO_input, *, n_iterations: int, return_features: bool = False):
         for _ in range(n_iterations):
             prep, x, pose, _, render_time = self._one_pass(
                 images, K, im_ids, obj_ids, TCO_input, n_img_channels=3, multiview_type="TCO", normalize=False,
-                render_normals=False, render_depth=False, depth_mode=0, want_pose=True, want_logits=False)
+                render_normals=False, render_depth=False, depth_mode=0, want_pose=True, want_logits=False,
+                want_features=return_features)
             TCO_output = ops.pose_update(TCO_input, prep["K_crop"], pose, None)
             images_crop, renders = self._pixels(x, 3, 3)
             yield dict(TCO_input=TCO_input, TCO_output=TCO_output, TCV_O=prep["TCV_O"], tCR=prep["tCR"],
                        KV_crop=prep["K_crop"], boxes_rend=prep["boxes_rend"], boxes_crop=prep["boxes_crop"],
-                       pose=pose, images_crop=images_crop, renders=renders, render_time=render_time)
+                       pose=pose, images_crop=images_crop, renders=renders, render_time=render_time,
+                       features=prep.get("features"))
             TCO_input = TCO_output
 
     def _build_outputs(self, recs, labels, K, per_hyp, im_ids) -> Dict[str, PosePredictorOutput]:
@@ -442,7 +468,9 @@ class CosyPosePosePredictor(_RenderAndCompare):
             outputs[f"iteration={n + 1}"] = PosePredictorOutput(
                 renders=r["renders"], images_crop=r["images_crop"], TCO_input=r["TCO_input"], TCO_output=r["TCO_output"],
                 TCV_O_input=r["TCV_O"], tCR=r["tCR"], labels=labels, K=Kb, K_crop=r["KV_crop"][:, 0],
-                KV_crop=r["KV_crop"], network_outputs={"pose": r["pose"]}, boxes_rend=r["boxes_rend"],
+                KV_crop=r["KV_crop"],
+                network_outputs={"pose": r["pose"], **({"features": r["features"]} if r.get("features") is not None else {})},
+                boxes_rend=r["boxes_rend"],
                 boxes_crop=r["boxes_crop"], timing_dict={"render": r["render_time"]})
         return outputs
 

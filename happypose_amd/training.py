@@ -9,7 +9,8 @@ losses are ``happypose_amd.losses``: every input and every intermediate stays on
 
 This is the step, not a trainer.  Each iteration's ``network_outputs["pose"]`` is marked ``requires_grad_()`` before the loss, so
 ``loss.backward()`` leaves ``dL/dpose`` in its ``.grad`` (``debug_dict["outputs"]["iteration=k"].network_outputs["pose"].grad``):
-the hand-over point for whatever trains a head.  Nothing here runs a network backward or an optimiser.
+the hand-over point for whatever trains a head.  The forward-loss functions run no network backward and no optimiser;
+``HeadTrainer`` (at the end of this module) is the consumer that does, for the linear heads on a frozen backbone.
 
 Differences from the reference, all deliberate:
 
@@ -40,7 +41,8 @@ import torch
 from . import detection_losses, losses, ops
 
 __all__ = ["AverageValueMeter", "TrainingConfig", "CosyPoseTrainingConfig", "DetectorTrainingConfig", "add_noise", "TCO_init_from_boxes",
-           "TCO_init_from_boxes_zup_autodepth", "make_hypotheses", "h_pose", "megapose_forward_loss", "h_maskrcnn"]
+           "TCO_init_from_boxes_zup_autodepth", "make_hypotheses", "h_pose", "megapose_forward_loss", "h_maskrcnn", "HeadOptimConfig",
+           "HeadTrainer"]
 
 MEGAPOSE_METHODS = ("coarse_z_up+auto-depth", "refiner_gt+noise")
 COSYPOSE_METHODS = ("fixed", "gt+noise", "fixed+trans_noise")
@@ -456,3 +458,174 @@ def h_maskrcnn(data, model, meters, cfg, *, seed: int = 0, debug_dict: Optional[
                           losses=dict(loss_rpn_box_reg=loss_rpn_box_reg, loss_objectness=loss_objectness, loss_box_reg=loss_box_reg,
                                       loss_classifier=loss_classifier, loss_mask=loss_mask))
     return loss
+
+
+# ---- training the linear heads on a frozen backbone ------------------------------------------------------------------------------
+@dataclass
+class HeadOptimConfig:
+    """The optimiser recipe of the reference's trainers.  Both construct ``torch.optim.Adam(lr=3e-4, weight_decay=0.0)`` -- L2,
+    not decoupled -- with torch's default ``betas`` and ``eps`` (``CP/training/train_pose.py:374-378``,
+    ``MP/training/utils.py:115-135`` with ``MP/training/training_config.py:113-118``), clip the total gradient norm
+    (``clip_grad_norm``: 1000.0 in ``training_config.py:115``, the default here; 0.5 in ``CP/scripts/run_pose_training.py:70``:
+    :meth:`cosypose`) and warm the learning rate up linearly over ``n_epochs_warmup = 50`` epochs of
+    ``epoch_size // batch_size = 115200 // 16`` batches with a ``LambdaLR``: step ``t = 1, 2, ...`` runs at
+    ``lr min(t / n_warmup_steps, 1)`` (``train_pose.py:387-392``, ``(batch + 1) / n_batches_warmup``; MegaPose's
+    ``max(batch, 1) / n_batches_warmup`` repeats the first value once).  ``n_warmup_steps = 0``: no warm-up.  The decay by 10
+    every ``lr_epoch_decay`` epochs belongs to a loop over a dataset and is not here.  ``clip_grad_norm = None``: no clipping."""
+
+    lr: float = 3e-4
+    betas: Tuple[float, float] = (0.9, 0.999)
+    eps: float = 1e-8
+    weight_decay: float = 0.0
+    decoupled: bool = False
+    clip_grad_norm: Optional[float] = 1000.0
+    n_warmup_steps: int = 50 * (115200 // 16)
+
+    @classmethod
+    def cosypose(cls, **kw) -> "HeadOptimConfig":
+        return cls(**{"clip_grad_norm": 0.5, **kw})
+
+    def lr_at(self, step: int) -> float:
+        """The learning rate of step ``step`` (counted from 1)."""
+        if self.n_warmup_steps <= 0:
+            return float(self.lr)
+        return float(self.lr) * min(step / self.n_warmup_steps, 1.0)
+
+
+class _WithFeatures:
+    """A predictor whose calls ask for the head input features; everything else is the predictor's."""
+
+    def __init__(self, model):
+        self._model = model
+
+    def __getattr__(self, name):
+        return getattr(self._model, name)
+
+    def __call__(self, **kw):
+        return self._model(return_features=True, **kw)
+
+
+class HeadTrainer:
+    """Fine-tunes the linear heads of a pose network on its frozen backbone: the pose rows, the rendered-view logits rows (they
+    receive a zero gradient while no loss reads them) and, on the torchvision-ResNet path, the 512 x 512 ``fc`` in front of them.
+
+    fp32 master copies of these tensors live in one flat device buffer ``p`` beside the gradient ``g`` and Adam's ``m`` / ``v``.
+    :meth:`step` is ``megapose_forward_loss`` / ``h_pose``, ``loss.backward()`` (which leaves ``dL/dpose`` at every iteration's
+    network output), then ``ops.head_backward`` per iteration -- summed with ``accumulate`` --, ``ops.fc_backward``,
+    ``ops.grad_sq_norm``, ``ops.adamw_step`` and ``ops.Net.set_param_device``: between ``backward()`` and the weight write
+    there are only launches and device-to-device copies on one stream, no host synchronisation.  The backbone's own backward
+    (and train-mode BatchNorm) is not built: ``d_feat`` of ``ops.head_backward`` is where it would attach."""
+
+    ORDER = ("pose_fc.weight", "views_logits_head.weight", "pose_fc.bias", "views_logits_head.bias", "backbone.fc.weight", "backbone.fc.bias")
+
+    def __init__(self, model, mesh_db, cfg, optim_cfg: Optional[HeadOptimConfig] = None, kind: str = "megapose"):
+        if kind not in ("megapose", "cosypose"):
+            raise ValueError(kind)
+        net = getattr(model, "backbone", None)
+        if not isinstance(net, ops.Net):
+            raise TypeError("HeadTrainer: the model must be a single-lane predictor of this library (model.backbone an ops.Net)")
+        if not net.pose_dim:
+            raise ValueError("HeadTrainer: the network has no pose head")
+        if optim_cfg is None:
+            optim_cfg = HeadOptimConfig() if kind == "megapose" else HeadOptimConfig.cosypose()
+        self.model, self.mesh_db, self.cfg, self.optim_cfg, self.kind = model, mesh_db, cfg, optim_cfg, kind
+        self.net, self.device = net, net.device
+        self.pose_dim, self.n_logits, self.n_features = int(net.pose_dim), int(net.n_logits), int(net.n_features)
+        shapes = net.head_param_shapes()
+        self.has_fc = "backbone.fc.weight" in shapes
+        self.shapes = {k: shapes[k] for k in self.ORDER if k in shapes}
+        n = sum(int(np.prod(sh)) for sh in self.shapes.values())
+        f = dict(dtype=torch.float32, device=self.device)
+        self.p, self.g = torch.empty(n, **f), torch.zeros(n, **f)
+        self.m, self.v = torch.zeros(n, **f), torch.zeros(n, **f)
+        self.n_steps = 0
+        self.params, self.grads = self._views(self.p), self._views(self.g)
+        for name, view in self.params.items():
+            net.get_param_device(name, out=view)
+        # the heads as ONE matrix [O, C] and one bias [O]: ORDER puts the pose rows and the logits rows next to each other
+        O, C = self.pose_dim + self.n_logits, self.n_features
+        self._W, self._gW, self._gb = self.p[:O * C].view(O, C), self.g[:O * C].view(O, C), self.g[O * C:O * C + O]
+        self._sq_norm = torch.zeros(1, **f)
+        clip = optim_cfg.clip_grad_norm
+        self._max_norm = None if clip is None else torch.full((1,), float(clip), **f)
+
+    def _views(self, flat: torch.Tensor) -> Dict[str, torch.Tensor]:
+        out, at = {}, 0
+        for name, shape in self.shapes.items():
+            k = int(np.prod(shape))
+            out[name] = flat[at:at + k].view(shape)
+            at += k
+        return out
+
+    def _forward_loss(self, batch, meters, n_iterations: int, seed: int, debug_dict, **kw) -> torch.Tensor:
+        model = _WithFeatures(self.model)
+        if self.kind == "megapose":
+            return megapose_forward_loss(model, self.cfg, batch, meters, self.mesh_db, n_iterations, debug_dict, seed=seed, **kw)
+        if not self.cfg.loss_disentangled:
+            raise NotImplementedError("HeadTrainer: the ADD-L1 loss leaves its gradient at TCO_output; the backward of the pose "
+                                      "update is not built (cfg.loss_disentangled = True)")
+        return h_pose(model, self.mesh_db, batch, meters, self.cfg, n_iterations, seed=seed, debug_dict=debug_dict, **kw)
+
+    def step(self, batch, meters, n_iterations: int = 1, seed: int = 0, *, debug_dict: Optional[Dict[str, Any]] = None, **kw) -> torch.Tensor:
+        """One optimiser step on ``batch``; returns ``loss_total`` of the forward (a device scalar, before the update) and adds
+        ``grad_norm`` (the total norm before clipping, as ``clip_grad_norm_`` returns it) and ``lr`` to ``meters`` beside the
+        forward-loss function's own.  ``debug_dict`` receives what the forward-loss function leaves there; ``kw`` goes to it
+        (``input_generator=`` for ``h_pose``)."""
+        dbg: Dict[str, Any] = {} if debug_dict is None else debug_dict
+        loss = self._forward_loss(batch, meters, n_iterations, seed, dbg, **kw)
+        loss.backward()
+        # from here to the weight write: launches and device-to-device copies on the current stream only
+        for k in range(n_iterations):
+            out = dbg["outputs"][f"iteration={k + 1}"].network_outputs
+            d_pose = out["pose"].grad
+            assert d_pose is not None, "the loss did not reach this iteration's pose output"
+            res = ops.head_backward(out["features"], d_pose.contiguous(), self._W, n_logits=self.n_logits, dW=self._gW, db=self._gb,
+                                    accumulate=k > 0, return_d_feat=self.has_fc)
+            if self.has_fc:
+                ops.fc_backward(res[2], out["pooled"], dW=self.grads["backbone.fc.weight"], db=self.grads["backbone.fc.bias"],
+                                accumulate=k > 0)
+        ops.grad_sq_norm(self.g, out=self._sq_norm)
+        self.n_steps += 1
+        oc = self.optim_cfg
+        lr = oc.lr_at(self.n_steps)
+        ops.adamw_step(self.p, self.g, self.m, self.v, lr=lr, betas=oc.betas, eps=oc.eps, weight_decay=oc.weight_decay, step=self.n_steps,
+                       decoupled=oc.decoupled, sq_norm=self._sq_norm if self._max_norm is not None else None, max_norm=self._max_norm)
+        self._write_heads()
+        meters["grad_norm"].add(math.sqrt(float(self._sq_norm)))  # the step's second read-back, after the weights are written
+        meters["lr"].add(lr)
+        return loss.detach()
+
+    def _write_heads(self) -> None:
+        for name, view in self.params.items():
+            self.net.set_param_device(name, view)
+
+    def state_dict(self) -> Dict[str, Any]:
+        """The head tensors under the reference's parameter names (update a checkpoint's ``state_dict`` with them and the model
+        loaders read the fine-tuned network) and the optimiser state under ``"optimizer"``: ``step`` and, per parameter name,
+        ``exp_avg`` / ``exp_avg_sq``.  Everything is a copy."""
+        m, v = self._views(self.m), self._views(self.v)
+        out: Dict[str, Any] = {name: t.clone() for name, t in self.params.items()}
+        out["optimizer"] = dict(step=self.n_steps, exp_avg={k: t.clone() for k, t in m.items()},
+                                exp_avg_sq={k: t.clone() for k, t in v.items()})
+        return out
+
+    def load_state_dict(self, state: Dict[str, Any]) -> None:
+        """The inverse of :meth:`state_dict`; the heads go into the network too.  Without ``"optimizer"`` the moments restart."""
+        missing = [k for k in self.shapes if k not in state]
+        if missing:
+            raise KeyError(f"HeadTrainer.load_state_dict: missing {missing}")
+        m, v = self._views(self.m), self._views(self.v)
+        for name, view in self.params.items():
+            src = torch.as_tensor(state[name])
+            assert tuple(src.shape) == tuple(view.shape), f"{name}: {tuple(src.shape)} for {tuple(view.shape)}"
+            view.copy_(src)
+        opt = state.get("optimizer")
+        if opt is None:
+            self.m.zero_(), self.v.zero_()
+            self.n_steps = 0
+        else:
+            self.n_steps = int(opt["step"])
+            for name in self.shapes:
+                m[name].copy_(torch.as_tensor(opt["exp_avg"][name]))
+                v[name].copy_(torch.as_tensor(opt["exp_avg_sq"][name]))
+        self._write_heads()

@@ -364,6 +364,17 @@ int hp_net_add_se(hp_net* net, const char* prefix, int C, int Cse, int H, int W,
 int hp_net_add_output(hp_net* net, int slot, int H, int W, int C);
 int hp_net_input_channels_padded(const hp_net* net);
 int hp_net_set_param(hp_net* net, const char* name, const float* h_data, int64_t numel);
+/* The device-pointer sibling of hp_net_set_param for a FINALISED network: an asynchronous device-to-device copy on `stream`,
+ * ordered like any launch, without a host round trip and without re-planning (head training: hp_adamw_step below).  Only the
+ * tensors the head kernels read as plain fp32 can be replaced: "pose_fc.weight" / ".bias", "views_logits_head.weight" / ".bias"
+ * and, on HP_ARCH_VANILLA_RESNET34, "backbone.fc.weight" / ".bias".  Every other name was folded or packed at finalise (conv and
+ * BN weights) and is HP_ERR_ARG, as are a wrong element count and a head the network does not have.
+ * hp_net_set_pooled_out: while d_pooled is not NULL every forward of a network with the fc also copies the fc's INPUT (the
+ * spatial mean, [batch][512]) to d_pooled, on the forward's stream -- what hp_fc_backward reads; NULL switches it off again. */
+int hp_net_set_param_device(hp_net* net, const char* name, const float* d_data, int64_t numel, void* stream);
+/* ... and the way back: the same tensors copied out of the network (a trainer's master copy starts from them); same errors. */
+int hp_net_get_param_device(hp_net* net, const char* name, float* d_data, int64_t numel, void* stream);
+int hp_net_set_pooled_out(hp_net* net, float* d_pooled);
 /* Arithmetic of the conv stack, to be chosen before hp_net_finalize:
  *   HP_PRECISION_F32 (default): fp32 MFMA, the reference's precision;
  *   HP_PRECISION_F16: weights / activations rounded to fp16 once per layer, fp32 accumulation
@@ -1384,6 +1395,62 @@ int hp_batch_gather_chw(int B, int h, int w, const uint8_t* d_rgb, const float* 
                         int n_out, uint8_t* d_out_rgb, float* d_out_depth, void* stream);
 int hp_instance_masks(int B, int h, int w, const int32_t* d_segmentation, const int32_t* d_ids, const int32_t* d_count,
                       const int32_t* d_slot_row, int max_ids, int G, uint8_t* d_masks, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * Training the linear heads on a frozen backbone (csrc/head_train.hip; the user-facing layer is happypose_amd.training.HeadTrainer).
+ * The heads are the ones csrc/pool_head.hip evaluates: out[b][o] = W[o] . feat[b] + bias[o], rows o = 0 .. pose_dim - 1 the pose
+ * head and pose_dim .. O - 1 the rendered-view logits (O = pose_dim + n_logits <= 32), feat [B][C] the spatial mean or, on the
+ * torchvision-ResNet path, the output of the 512 x 512 fc (the features output of hp_net_forward).  The optimiser is the one the
+ * reference's trainers construct (CP/training/train_pose.py:374-378, MP/training/utils.py:115-135: torch.optim.Adam), its clipping
+ * torch.nn.utils.clip_grad_norm_ (train_pose.py:438-442, MP/training/train_megapose.py:360-363).  All fp32.  No floating-point
+ * atomics: every sum has one order that depends on the sizes alone -- results are bit-identical from run to run and independent of
+ * the launch grid.  u = 2^-24 below.
+ *
+ * hp_head_backward    g[b][o] = w[b] d_out[b][o], rounded once (d_w == NULL: g = d_out, no product); d_out is given in two parts,
+ *                     d_pose_grad [B][pose_dim] and d_logit_grad [B][n_logits], and a NULL d_logit_grad stands for zeros.
+ *                       dW[o][c]     = sum_b g[b][o] feat[b][c]         [O][C]
+ *                       db[o]        = sum_b g[b][o]                    [O]
+ *                       d_dfeat[b][c] = sum_o g[b][o] W[o][c]           [B][C], optional (NULL: not computed; it needs d_W [O][C]):
+ *                                                                        what hp_fc_backward, and later a backbone's backward, reads
+ *                     Order of the sum over b: rows are cut into chunks of 64 in index order (chunk k = rows 64 k .. 64 k + 63);
+ *                     inside a chunk acc = fma(g, feat, acc) from acc = 0 in row order (db: plain additions); the chunks' partial
+ *                     sums are added in index order, s = p_0, s += p_k; with accumulate != 0 the result is then ADDED to what
+ *                     dW / db hold (dW = dW + s), else it replaces it.  A term meets at most B + 2 roundings, so
+ *                     |dW - exact| <= (B + 2) u sum_b |g feat| per element.  d_dfeat is an fma chain over o = 0 .. O - 1 from 0.
+ *                     d_ws: hp_head_backward_ws_floats(B, C, O) = ceil(B / 64) (O C + O) floats.  B == 0: zeros (or nothing added).
+ * hp_fc_backward      the same reduction for a layer with many outputs, dW[o][c] = sum_b d_dout[b][o] d_in[b][c] ([O][C];
+ *                     the fc: O = C = 512, d_dout the d_dfeat above, d_in the pooled input of hp_net_set_pooled_out) and
+ *                     db[o] = sum_b d_dout[b][o].  Here the outputs supply the parallelism and the sum over b is ONE chain in row
+ *                     order per element, acc = fma(d_dout, d_in, acc) from 0 (db: plain additions); accumulate as above.
+ * hp_grad_sq_norm     d_sq_norm[0] = sum_i g[i]^2 over a flat buffer, N <= 2^31 - 1.  Two levels: workgroup k of 256 lanes takes
+ *                     elements 1024 k .. 1024 k + 1023, lane t the four x_j = g[1024 k + t + 256 j] (0 past N) as
+ *                     (x0 x0 + x1 x1) + (x2 x2 + x3 x3); the 64 lanes of a wavefront meet in a butterfly (partner lane ^ 1, ^ 2,
+ *                     .. ^ 32), the four wavefronts as (s0 + s1) + (s2 + s3).  With more than one workgroup a second launch of ONE
+ *                     workgroup adds the partials: lane t takes t, t + 256, ... in index order, then the same butterfly and wave
+ *                     sum.  d_ws: hp_grad_sq_norm_ws_floats(N) = ceil(N / 1024) floats (not read when that is 1).
+ * hp_adamw_step       one launch over p, g, m, v [N]; g is not written.  step counts from 1.  With d_sq_norm and d_max_norm (device
+ *                     scalars, both or neither) the gradient is first clipped as clip_grad_norm_ does, inside the launch -- no host
+ *                     read-back between the backward and the step:
+ *                       g = g min(max_norm / (sqrt(sq_norm) + 1e-6), 1)
+ *                     then, in the order of torch's _single_tensor_adam (torch/optim/adam.py), every operation rounded once to fp32:
+ *                       weight_decay != 0:  decoupled == 0 (Adam, L2):  g = g + weight_decay p
+ *                                           decoupled != 0 (AdamW):     p = p (1 - lr weight_decay)
+ *                       m = m + (1 - beta1) (g - m)                      exp_avg.lerp_(grad, 1 - beta1)
+ *                       v = v beta2;  v = v + (1 - beta2) (g g)          exp_avg_sq.mul_(beta2).addcmul_(grad, grad, value=1 - beta2)
+ *                       denom = sqrt(v) / sqrt(1 - beta2^step) + eps
+ *                       p = p + (-(lr / (1 - beta1^step))) (m / denom)   param.addcdiv_(exp_avg, denom, value=-step_size)
+ *                     The scalars 1 - beta1, 1 - beta2, 1 - lr weight_decay, lr / (1 - beta1^step), sqrt(1 - beta2^step) are formed
+ *                     on the host in double, as torch forms them from Python floats, and rounded to fp32 once.
+ * ---------------------------------------------------------------------------------- */
+int64_t hp_head_backward_ws_floats(int B, int C, int O);
+int hp_head_backward(int B, int C, int pose_dim, int n_logits, const float* d_feat, const float* d_pose_grad, const float* d_logit_grad,
+                     const float* d_w, const float* d_W, int accumulate, float* d_dW, float* d_db, float* d_dfeat, float* d_ws,
+                     int64_t ws_floats, void* stream);
+int hp_fc_backward(int B, int O, int C, const float* d_dout, const float* d_in, int accumulate, float* d_dW, float* d_db, void* stream);
+int64_t hp_grad_sq_norm_ws_floats(int64_t N);
+int hp_grad_sq_norm(int64_t N, const float* d_g, float* d_sq_norm, float* d_ws, int64_t ws_floats, void* stream);
+int hp_adamw_step(int64_t N, float* d_p, const float* d_g, float* d_m, float* d_v, double lr, double beta1, double beta2, double eps,
+                  double weight_decay, int64_t step, int decoupled, const float* d_sq_norm, const float* d_max_norm, void* stream);
 
 #if defined(__GNUC__) || defined(__clang__)
 #pragma GCC visibility pop

@@ -20,11 +20,12 @@
 #include <cfloat>
 
 #include "common.h"
+#include "philox.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int kLine = 1024;    // the longest line the blur's LDS paths take
 constexpr int kColTile = 8;    // columns per workgroup of blur_cols_kernel: 24 bytes = 6 dwords per row
@@ -32,20 +33,6 @@ constexpr int kImgThreads = 1024;  // missing_kernel / ellipse_prep_kernel: one 
 constexpr int kImgWaves = kImgThreads / kWave;
 constexpr int64_t kMaxPixels = int64_t(1) << 28;
 constexpr uint32_t kStreamNoise = HP_AUG_STREAM_NOISE, kStreamGrid = HP_AUG_STREAM_GRID, kStreamMissing = HP_AUG_STREAM_MISSING;
-
-__device__ inline void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[0] = n0, c[1] = (uint32_t)p1, c[2] = n2, c[3] = (uint32_t)p0;
-}
-
-__device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-}
 
 // Box-Muller on the 24 high bits of words 0 and 1 of counter (index, image, stream, 0)
 __device__ inline float normal_deviate(uint32_t index, uint32_t image, uint32_t stream, uint32_t k0, uint32_t k1) {
@@ -104,8 +91,7 @@ __global__ void __launch_bounds__(kThreads) gray_sum_kernel(const uint8_t* __res
     for (int i = 0; i < 4; ++i)
       if (i < n) acc += (unsigned)gray_of(c[3 * i], c[3 * i + 1], c[3 * i + 2]);
   }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) acc += __shfl_down(acc, off, kWave);
+  acc = wave_sum(acc);
   if (threadIdx.x % kWave == 0) s_part[threadIdx.x / kWave] = acc;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -416,8 +402,7 @@ __global__ void __launch_bounds__(kThreads) depth_mask_kernel(const float* depth
 
 // sum of one int per thread over the workgroup of kImgThreads, to every thread; s_red [kImgWaves] is free again on return
 __device__ inline int block_sum(int v, int* s_red) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_down(v, off, kWave);
+  v = wave_sum(v);
   if (threadIdx.x % kWave == 0) s_red[threadIdx.x / kWave] = v;
   __syncthreads();
   int t = 0;
@@ -600,7 +585,7 @@ struct Workspace {
   float* recs;               // [B][E][8]
 };
 
-inline int64_t region_bytes(int B, int64_t hw) { return (4 * (int64_t)B * hw + 7) / 8 * 8; }
+inline int64_t region_bytes(int B, int64_t hw) { return round_up(4 * (int64_t)B * hw, 8); }
 inline int64_t ws_bytes(int B, int64_t hw, int E) { return 8 * (int64_t)B + region_bytes(B, hw) + 32 * (int64_t)B * E; }
 
 inline Workspace carve(void* ws, int B, int64_t hw) {
@@ -608,7 +593,6 @@ inline Workspace carve(void* ws, int B, int64_t hw) {
   return {reinterpret_cast<unsigned long long*>(p), p + 8 * (int64_t)B, reinterpret_cast<float*>(p + 8 * (int64_t)B + region_bytes(B, hw))};
 }
 
-inline bool aligned(const void* p, int n) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(n - 1)) == 0; }
 inline dim3 pixel_grid(int64_t items, int B) { return dim3((unsigned)((items + kThreads - 1) / kThreads), (unsigned)B); }
 
 }  // namespace

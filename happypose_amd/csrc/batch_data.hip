@@ -7,7 +7,7 @@
 //                   chunk of 64 slots are one ballot, the number of valid slots the sum of four population counts, and the k-th
 //                   valid slot is the lane whose flag is set with k flags set below it (a second ballot).  k is 0 (first) or
 //                   mulhi32(x0, n_valid), x0 = word 0 of Philox4x32-10, key (seed lo, seed hi), counter (row lo, row hi, 0, 0),
-//                   row = row_offset + b in 64 bits: the rounds and the key layout of csrc/train_hyp.hip.  Lanes 0 .. 15 then
+//                   row = row_offset + b in 64 bits: the generator of philox.h, the key layout of csrc/train_hyp.hip.  Lanes 0 .. 15 then
 //                   evaluate one entry each of inverse(TWC) @ TWO[chosen] in double from the float32 inputs, in the order written
 //                   in the header, and round once.
 //   scan_kernel     one workgroup: the exclusive scan of the valid flags over the frames, 256 frames per step (ballot, population
@@ -28,13 +28,14 @@
 // Integers and copied bits only, except the pose product; no atomics; every output element has one writer: two calls give the same
 // bits.  Every index that comes from device memory (count, dst, slot_row) is checked against the table it addresses before use.
 #include "common.h"
+#include "philox.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
 #pragma clang fp contract(off)  // the pose product rounds in the order written
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kMaxIds = 256;  // as hp_seg_boxes
@@ -42,19 +43,9 @@ constexpr int kTile = 4096;   // pixels per workgroup of gather_kernel and masks
 constexpr int kPlane = kTile + 16;           // bytes of one LDS plane of gather_kernel: the tile and the largest shift, a multiple of 16
 constexpr int kSegWords = kTile + kTile / 16;  // padded words of the staged id map
 
-__device__ inline void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[0] = n0, c[1] = (uint32_t)p1, c[2] = n2, c[3] = (uint32_t)p0;
-}
-
 __device__ inline uint32_t philox_word0(uint64_t row, uint32_t k0, uint32_t k1) {
   uint32_t c[4] = {(uint32_t)row, (uint32_t)(row >> 32), 0u, 0u};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
+  philox4x32_10(c, k0, k1);
   return c[0];
 }
 

@@ -39,6 +39,10 @@ inline int check_launch(const char* what) {
   return HP_OK;
 }
 
+// launcher helpers: is p on a `bytes` grid (a power of two); v rounded up to a multiple of m
+inline bool aligned(const void* p, int bytes) { return (reinterpret_cast<uintptr_t>(p) & (uintptr_t)(bytes - 1)) == 0; }
+inline int64_t round_up(int64_t v, int64_t m) { return (v + m - 1) / m * m; }
+
 // First-launch set-up of ONE kernel instantiation (dynamic-LDS opt-in, scratch query): `static FirstLaunch fl;` in its launcher,
 // `fl.once([&](FirstLaunch& s) { ...; return HP_OK; })` runs the set-up exactly once per process whichever host thread launches
 // first -- concurrent first launches on distinct streams wait for it instead of racing on a plain flag -- and

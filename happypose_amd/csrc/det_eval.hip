@@ -15,25 +15,19 @@
 //                      by a wave butterfly on (class, IoU, position).  Ground truth j is read AND marked by lane j % 64 only, so the
 //                      matched flags need no fence.
 #include "common.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int kPackSteps = 4;                               // 8-byte groups per thread
 constexpr int kChunkWords = kThreads * kPackSteps / 8;      // 128 words = 8192 pixels per workgroup
 constexpr int64_t kMaxPlane = int64_t(1) << 24;             // every count is exact in float32
 
-__device__ inline int wave_add(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // sum over the workgroup, valid in thread 0
 __device__ inline int block_add(int v, int* s_red) {
-  v = wave_add(v);
+  v = wave_sum(v);
   const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
   if (lane == 0) s_red[wave] = v;
   __syncthreads();
@@ -211,8 +205,6 @@ __global__ void __launch_bounds__(kWave) match_kernel(MatchParams p, int32_t* __
   }
 }
 
-inline bool aligned8(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 7) == 0; }
-
 }  // namespace
 }  // namespace hp
 
@@ -229,13 +221,13 @@ extern "C" int hp_mask_pack(int n, int h, int w, const uint8_t* d_masks, uint64_
   HP_REQUIRE((int64_t)h * w <= kMaxPlane, "hp_mask_pack: more than 2^24 pixels per mask");
   if (n == 0) return HP_OK;
   HP_REQUIRE(d_masks && d_words && d_area, "hp_mask_pack: null pointer");
-  HP_REQUIRE(aligned8(d_words), "hp_mask_pack: d_words must be 8-byte aligned");
+  HP_REQUIRE(aligned(d_words, 8), "hp_mask_pack: d_words must be 8-byte aligned");
   const int64_t P = (int64_t)h * w;
   const int w64 = (int)hp_mask_pack_words(h, w);
   hipStream_t st = (hipStream_t)stream;
   HP_CHECK_HIP(hipMemsetAsync(d_area, 0, (size_t)n * sizeof(int32_t), st));
   const dim3 grid((unsigned)n, (unsigned)((w64 + kChunkWords - 1) / kChunkWords));  // at most 2^18 / 128 chunks
-  if (P % 8 == 0 && aligned8(d_masks))
+  if (P % 8 == 0 && aligned(d_masks, 8))
     hipLaunchKernelGGL(pack_kernel<true>, grid, dim3(kThreads), 0, st, d_masks, P, w64, d_words, d_area);
   else
     hipLaunchKernelGGL(pack_kernel<false>, grid, dim3(kThreads), 0, st, d_masks, P, w64, d_words, d_area);
@@ -255,7 +247,7 @@ extern "C" int hp_det_iou(int n_rows, const int32_t* d_pred_idx, const int32_t* 
   HP_REQUIRE(d_pred_idx && d_gt_idx, "hp_det_iou: null index column");
   HP_REQUIRE(!boxes || d_box_iou, "hp_det_iou: boxes given without d_box_iou");
   HP_REQUIRE(!masks || (d_inter && d_union && d_mask_iou), "hp_det_iou: masks given without d_inter, d_union and d_mask_iou");
-  HP_REQUIRE(!masks || (aligned8(d_words_pred) && aligned8(d_words_gt)), "hp_det_iou: packed masks must be 8-byte aligned");
+  HP_REQUIRE(!masks || (aligned(d_words_pred, 8) && aligned(d_words_gt, 8)), "hp_det_iou: packed masks must be 8-byte aligned");
   IouParams p;
   p.pred_idx = d_pred_idx, p.gt_idx = d_gt_idx, p.boxes_pred = d_boxes_pred, p.boxes_gt = d_boxes_gt;
   p.words_pred = d_words_pred, p.words_gt = d_words_gt, p.area_pred = d_area_pred, p.area_gt = d_area_gt;

@@ -15,13 +15,14 @@
 //                      partial per workgroup goes to the workspace and sum_kernel (one workgroup) adds the partials in a fixed
 //                      order.  No atomics: two calls give the same bits, and a row's gradient is a function of the row alone.
 #include "common.h"
+#include "philox.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
 #pragma clang fp contract(off)  // box_iou is compiled into two kernels whose results are compared for equality
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kChunk = 4096;  // boxes per workgroup of gt_max_kernel
@@ -60,8 +61,7 @@ __global__ void __launch_bounds__(kThreads) gt_max_kernel(int n, const float* __
     const float v = box_iou(gb, boxes + 4 * i);
     if (v > best) best = v;
   }
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) best = fmaxf(best, __shfl_xor(best, off, kWave));
+  best = wave_max(best);
   if (tid % kWave == 0) s_red[tid / kWave] = best;
   __syncthreads();
   if (tid == 0) {
@@ -115,23 +115,13 @@ __global__ void __launch_bounds__(kThreads) assign_kernel(int n, const float* __
   iou[i] = best;
 }
 
-// ---- Philox4x32-10 (the rounds of csrc/train_hyp.hip) ---------------------------------------------------------------------------
-__device__ inline void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[0] = n0, c[1] = (uint32_t)p1, c[2] = n2, c[3] = (uint32_t)p0;
-}
-
+// ---- one Philox4x32-10 call (philox.h), counter (index in image, image, stream, 0), word 0 --------------------------------------------
 __global__ void __launch_bounds__(kThreads) keys_kernel(int n, const int32_t* __restrict__ index_in_image, const int32_t* __restrict__ image_of,
                                                         uint32_t stream_id, uint32_t k0, uint32_t k1, uint32_t* __restrict__ keys) {
   const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
   if (i >= n) return;
   uint32_t c[4] = {(uint32_t)index_in_image[i], (uint32_t)image_of[i], stream_id, 0u};
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
+  philox4x32_10(c, k0, k1);
   keys[i] = c[0];
 }
 
@@ -218,12 +208,6 @@ __global__ void __launch_bounds__(kThreads) mask_targets_kernel(const uint8_t* _
 }
 
 // ---- sums ---------------------------------------------------------------------------------------------------------------------------
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-
 // the workgroup's sums of NS values, valid in thread 0: lane, wavefront butterfly, LDS in wavefront order
 template <int NS>
 __device__ inline void block_sums(double v[NS], double (*s_red)[NS]) {
@@ -394,8 +378,6 @@ __global__ void __launch_bounds__(kThreads) mask_loss_kernel(int C, int P, const
 
 inline unsigned blocks_of(int64_t n) { return (unsigned)((n + kThreads - 1) / kThreads); }
 
-inline int64_t roundup8(int64_t v) { return (v + 7) / 8 * 8; }
-
 }  // namespace
 }  // namespace hp
 
@@ -404,7 +386,7 @@ using namespace hp;
 extern "C" int64_t hp_det_assign_workspace_bytes(int n, int n_gt) {
   if (n < 0 || n_gt < 0) return -1;
   const int64_t chunks = ((int64_t)n + kChunk - 1) / kChunk;
-  return roundup8(((int64_t)n_gt * chunks + n_gt) * (int64_t)sizeof(float));
+  return round_up(((int64_t)n_gt * chunks + n_gt) * (int64_t)sizeof(float), 8);
 }
 
 extern "C" int hp_det_assign(int n, const float* d_boxes, const int32_t* d_image_of, int n_images, const float* d_gt, int n_gt,

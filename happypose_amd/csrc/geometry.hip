@@ -4,6 +4,7 @@
 // TB/lib3d/multiview.py:189-190,212-222).  Here: one launch before the render
 // (hp_pose_prep) and one after the network (hp_pose_update).
 #include "common.h"
+#include "wave.h"
 
 namespace hp {
 
@@ -88,17 +89,6 @@ __device__ __forceinline__ void view_pose(const float* T, int v, float* TV) {
     }
   }
   TV[12] = T[12]; TV[13] = T[13]; TV[14] = T[14]; TV[15] = T[15];
-}
-
-__device__ __forceinline__ float wave_min(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fminf(v, __shfl_xor(v, o));
-  return v;
-}
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o));
-  return v;
 }
 
 struct PrepArgs {

@@ -143,7 +143,8 @@ __global__ __launch_bounds__(256) void fc_bwd(int B, int O, int C, const float* 
   }
 }
 
-// sum over the 256 threads of a workgroup, the same value in every lane of wavefront 0: butterfly, then (s0 + s1) + (s2 + s3)
+// sum over the 256 threads of a workgroup, the same value in every lane of wavefront 0: butterfly, then (s0 + s1) + (s2 + s3).
+// Not wave.h's wave_sum: the offsets run 1, 2, ... 32 here, another rounding order, and the trained weights are pinned to it.
 __device__ __forceinline__ float block_sum(float s, float* red) {
 #pragma unroll
   for (int off = 1; off < 64; off <<= 1) s += __shfl_xor(s, off);

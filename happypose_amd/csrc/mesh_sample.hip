@@ -17,11 +17,12 @@
 //                      F - 1), integer reflection of the 24-bit (ia, ib), p = (v0 + a (v1 - v0)) + b (v2 - v0) in fp32 without
 //                      contraction.  An object whose total is not a positive finite number gives NaN points and face_id -1.
 #include "common.h"
+#include "philox.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kScanChunk = 1024;  // faces per scan step = threads of the scan workgroup
 constexpr int kScanThreads = kScanChunk;
 constexpr int kScanWaves = kScanThreads / kWave;
@@ -97,20 +98,6 @@ __global__ void __launch_bounds__(kScanThreads) area_scan_kernel(const float* __
   }
 }
 
-__device__ inline void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[0] = n0, c[1] = (uint32_t)p1, c[2] = n2, c[3] = (uint32_t)p0;
-}
-
-__device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-}
-
 __global__ void __launch_bounds__(kSampleThreads) sample_kernel(const float* __restrict__ vertices, const int32_t* __restrict__ faces,
                                                                 const int32_t* __restrict__ vert_offset,
                                                                 const int32_t* __restrict__ face_offset, int n_samples, uint32_t key0,
@@ -178,7 +165,7 @@ extern "C" int hp_mesh_sample_surface(int n_obj, const float* d_vertices, const 
   // the face capacity of the tables is what the workspace was sized for: offsets past it are guarded on the device
   const int64_t cap_faces = workspace_bytes / (int64_t)sizeof(double) - n_obj;
   HP_REQUIRE(d_workspace && cap_faces >= 0, "hp_mesh_sample_surface: workspace smaller than hp_mesh_sample_workspace_bytes(n_obj, total_faces)");
-  HP_REQUIRE((reinterpret_cast<uintptr_t>(d_workspace) & 7) == 0, "hp_mesh_sample_surface: d_workspace must be 8-byte aligned");
+  HP_REQUIRE(aligned(d_workspace, 8), "hp_mesh_sample_surface: d_workspace must be 8-byte aligned");
   HP_REQUIRE(cap_faces == 0 || (d_vertices && d_faces), "hp_mesh_sample_surface: null mesh tables");
   hipStream_t st = (hipStream_t)stream;
   double* total = (double*)d_workspace;

@@ -12,11 +12,12 @@
 // No float atomics; every reduction is a fixed tree, so a row's outputs are a function of the row alone: the number of rows in the
 // launch, their modes and the run cannot change a bit.
 #include "common.h"
+#include "rigid.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kRowsPerBlock = 4;                      // rows_kernel: 256 threads
 constexpr int kPredTile = HP_POSE_ERR_PRED_TILE;      // predicted points per LDS tile (float4 each: 8 KB)
 constexpr int kGtBlock = HP_POSE_ERR_GT_BLOCK;        // ground-truth points per workgroup
@@ -24,66 +25,6 @@ constexpr int kAddsThreads = 256;
 constexpr int kGtPerLane = kGtBlock / kAddsThreads;   // 4
 constexpr int kPartial = 8;                           // floats per (row, block): sum |d|, sum |dx| |dy| |dz|, max |d|, 3 unused
 static_assert(kGtBlock % kAddsThreads == 0 && kPredTile % kAddsThreads == 0, "tile sizes are multiples of the workgroup");
-
-struct T34 {  // upper 3 x 4 of a row-major 4 x 4
-  float m[12];
-};
-
-__device__ inline T34 load_T(const float* __restrict__ p) {
-  T34 t;
-#pragma unroll
-  for (int i = 0; i < 12; ++i) t.m[i] = p[i];
-  return t;
-}
-
-__device__ inline T34 mul(const T34& a, const T34& b) {
-  T34 c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float s = j == 3 ? a.m[4 * i + 3] : 0.f;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) s = fmaf(a.m[4 * i + k], b.m[4 * k + j], s);
-      c.m[4 * i + j] = s;
-    }
-  }
-  return c;
-}
-
-__device__ inline void apply(const T34& t, float x, float y, float z, float& ox, float& oy, float& oz) {
-  ox = fmaf(t.m[0], x, fmaf(t.m[1], y, fmaf(t.m[2], z, t.m[3])));
-  oy = fmaf(t.m[4], x, fmaf(t.m[5], y, fmaf(t.m[6], z, t.m[7])));
-  oz = fmaf(t.m[8], x, fmaf(t.m[9], y, fmaf(t.m[10], z, t.m[11])));
-}
-
-// K @ T[:3]
-__device__ inline T34 camera_matrix(const float* __restrict__ K, const T34& t) {
-  T34 c;
-#pragma unroll
-  for (int i = 0; i < 3; ++i) {
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      float s = 0.f;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) s = fmaf(K[3 * i + k], t.m[4 * k + j], s);
-      c.m[4 * i + j] = s;
-    }
-  }
-  return c;
-}
-
-// xor butterflies: float addition and fmaxf are commutative, so every lane ends with the same bits
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ inline float wave_max(float v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, kWave));
-  return v;
-}
 
 struct Tables {
   const int32_t* pred_id;

@@ -17,13 +17,13 @@
 // accumulated in double, per lane in point order, then over the wavefront by xor butterflies, then over the four wavefronts in
 // LDS in wavefront order.  No atomics: a row's outputs are a function of the row alone and the same bits in every run.
 #include "common.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
 #pragma clang fp contract(off)  // the prologue is compiled into two kernels: both must give the predicted poses the same bits
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int kWaves = kThreads / kWave;
 constexpr int kSymChunk = HP_POSE_LOSS_SYM_CHUNK;
@@ -149,13 +149,6 @@ __device__ inline void apply(const float* t, float x, float y, float z, float* o
   o[0] = fmaf(t[0], x, fmaf(t[1], y, fmaf(t[2], z, t[3])));
   o[1] = fmaf(t[4], x, fmaf(t[5], y, fmaf(t[6], z, t[7])));
   o[2] = fmaf(t[8], x, fmaf(t[9], y, fmaf(t[10], z, t[11])));
-}
-
-// xor butterfly: addition is commutative, so every lane ends with the same bits
-__device__ inline double wave_sum(double v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
 }
 
 template <int NT>

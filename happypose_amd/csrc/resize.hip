@@ -236,8 +236,7 @@ __global__ __launch_bounds__(kThreads) void seg_boxes_kernel(const int32_t* __re
     }
 }
 
-inline bool aligned4(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3) == 0; }
-inline int64_t tmp_bytes(int B, int in_h, int out_w) { return ((int64_t)B * in_h * out_w * 3 + 7) / 8 * 8; }
+inline int64_t tmp_bytes(int B, int in_h, int out_w) { return round_up((int64_t)B * in_h * out_w * 3, 8); }
 
 }  // namespace
 }  // namespace hp
@@ -295,7 +294,7 @@ extern "C" int hp_resize_rgb(int B, int in_h, int in_w, int out_h, int out_w, co
   if (pass_y) {
     const uint8_t* src = pass_x ? tmp : d_in;
     const int row_bytes = 3 * out_w;
-    const bool vec = row_bytes % 4 == 0 && aligned4(src) && aligned4(d_out);
+    const bool vec = row_bytes % 4 == 0 && aligned(src, 4) && aligned(d_out, 4);
     const int items = vec ? row_bytes / 4 : row_bytes;
     const dim3 grid((unsigned)((items + kThreads - 1) / kThreads), (unsigned)out_h, (unsigned)B);
     if (vec)

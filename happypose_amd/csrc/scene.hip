@@ -20,11 +20,11 @@
 // is at most one pixel wide.  Depth, ids, mask and the visibility table are exact, and in the single-sample state (no
 // HP_RASTER_MSAA4) the colour too is exactly what one shared z-buffer gives.  A multi-object rasteriser pass is out of scope.
 #include "common.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int kVisRows = 16;       // image rows per visibility workgroup (4 wavefronts, 4 rows each)
 constexpr int kTileW = 64, kTileH = 4;  // contour tile: one wavefront per row
@@ -136,22 +136,6 @@ __global__ void __launch_bounds__(kThreads) visibility_init_kernel(int n, int32_
   if (i < n) table[i] = (i % HP_SCENE_VIS_FIELDS) < 2 ? 0 : -1;
 }
 
-__device__ inline int wave_add(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
-__device__ inline int wave_min(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = min(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-__device__ inline int wave_max(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off, kWave));
-  return v;
-}
-
 __global__ void __launch_bounds__(kThreads)
 visibility_kernel(int n_cam, const int32_t* __restrict__ layer_off, int n_layers, int H, int W, const float* __restrict__ l_depth,
                   const int32_t* __restrict__ ids, int32_t* __restrict__ table) {
@@ -190,7 +174,7 @@ visibility_kernel(int n_cam, const int32_t* __restrict__ layer_off, int n_layers
 #pragma unroll
   for (int k = 0; k < HP_SCENE_VIS_FIELDS; ++k) {
     const bool is_min = k == 2 || k == 3 || k == 6 || k == 7;
-    acc[k] = k < 2 ? wave_add(acc[k]) : (is_min ? wave_min(acc[k]) : wave_max(acc[k]));
+    acc[k] = k < 2 ? wave_sum(acc[k]) : (is_min ? wave_min(acc[k]) : wave_max(acc[k]));
     if (lane == 0) s_red[wave][k] = acc[k];
   }
   __syncthreads();
@@ -286,8 +270,6 @@ overlay_kernel(int64_t n_px, const uint8_t* __restrict__ input, const uint8_t* _
 
 static_assert(kThreads == 256 && kTileW * kTileH == kThreads, "overlay tables and contour tiles are one entry per thread");
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
-
 // shared shape checks: sizes the 64-bit pixel arithmetic and the launch grids hold
 inline const char* check_frame(int n_cam, int h, int w) {
   if (n_cam < 0) return "negative n_cam";
@@ -315,8 +297,8 @@ extern "C" int hp_scene_compose(int n_cam, const int32_t* d_layer_off, int n_lay
   const int64_t groups = (P + 3) / 4;
   const int64_t blocks = (groups + kThreads - 1) / kThreads;
   HP_REQUIRE(blocks < (int64_t(1) << 31), "hp_scene_compose: frame too large");
-  const bool vec = P % 4 == 0 && aligned16(d_layer_rgb) && aligned16(d_layer_nrm) && aligned16(d_layer_depth) && aligned16(d_rgb) &&
-                   aligned16(d_nrm) && aligned16(d_depth) && aligned16(d_ids) && aligned16(d_mask);
+  const bool vec = P % 4 == 0 && aligned(d_layer_rgb, 16) && aligned(d_layer_nrm, 16) && aligned(d_layer_depth, 16) && aligned(d_rgb, 16) &&
+                   aligned(d_nrm, 16) && aligned(d_depth, 16) && aligned(d_ids, 16) && aligned(d_mask, 16);
   hipStream_t st = (hipStream_t)stream;
   const dim3 grid((unsigned)blocks, (unsigned)n_cam);
   if (vec)

@@ -38,12 +38,13 @@
 #include <cmath>
 
 #include "common.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
 constexpr int kThreads = 1024;          // one workgroup per prediction
-constexpr int kWaves = kThreads / 64;
+constexpr int kWaves = kThreads / kWave;
 constexpr int kMaxM = 1024;             // correspondences per prediction
 constexpr int kWords = kMaxM / 32;      // words of a bit row
 constexpr double kCbar2 = 1.0;
@@ -178,13 +179,8 @@ __global__ __launch_bounds__(kThreads) void teaser_gather_kernel(const float* pt
 }
 
 // ---- solve ----------------------------------------------------------------------------------------------
-// sum over the workgroup, stage 1: lanes by xor-shuffle (every lane ends with the wave's sum), lane 0 -> part[wave]
-__device__ __forceinline__ double wave_sum(double s) {
-#pragma unroll
-  for (int off = 32; off > 0; off >>= 1) s += __shfl_xor(s, off);
-  return s;
-}
-// stage 2: the 16 waves in turn (every thread computes the same value)
+// sum over the workgroup: stage 1 is wave_sum (every lane ends with the wave's sum), lane 0 -> part[wave]; stage 2: the 16 waves
+// in turn (every thread computes the same value)
 __device__ __forceinline__ double waves_sum(const double* part, int stride) {
   double s = 0.0;
   for (int w = 0; w < kWaves; ++w) s += part[w * stride];
@@ -338,8 +334,7 @@ __global__ __launch_bounds__(kThreads) void teaser_solve_kernel(SolveArgs g) {
     for (int w = 0; w < kWords; ++w) deg += __popc(row[w] & sh_C[w]);
     int key = inC ? (deg << 10) | (kMaxM - 1 - tid) : -1;  // largest degree, then lowest index
     const bool full = !inC || deg == cnt - 1;
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) { const int o = __shfl_xor(key, off); key = o > key ? o : key; }
+    key = wave_max(key);
     const int allfull = __all(full);
     if (lane == 0) { sh_key[buf][wave] = key; sh_full[buf][wave] = allfull; }
     __syncthreads();
@@ -420,9 +415,7 @@ __global__ __launch_bounds__(kThreads) void teaser_solve_kernel(SolveArgs g) {
         }
       }
       const double cs = wave_sum(wgt * r2);  // the cost of the weights that produced R
-      double mx = r2;
-#pragma unroll
-      for (int off = 32; off > 0; off >>= 1) mx = fmax(mx, __shfl_xor(mx, off));
+      const double mx = wave_max(r2);
       if (lane == 0) { sh_partC[wave] = cs; sh_partX[wave] = mx; }
       __syncthreads();
       const double cost = waves_sum(sh_partC, 1);
@@ -540,21 +533,20 @@ __global__ __launch_bounds__(kThreads) void teaser_solve_kernel(SolveArgs g) {
 }
 
 constexpr int64_t kAlign = 256;
-inline int64_t aligned(int64_t bytes) { return (bytes + kAlign - 1) / kAlign * kAlign; }
 
 // sections of the refinement's workspace, in order
 struct Workspace {
   int64_t pts_a, pix, mind, count, indices, a, b, m_sel, total;
   Workspace(int64_t n, int64_t HW, int64_t n_points) {
     int64_t o = 0;
-    pts_a = o; o += aligned(n * HW * 3 * 4);
-    pix = o; o += aligned(n * HW * 4);
-    mind = o; o += aligned(n * HW * 4);
-    count = o; o += aligned(n * 4);
-    indices = o; o += aligned(n * n_points * 4);
-    a = o; o += aligned(n * n_points * 3 * 4);
-    b = o; o += aligned(n * n_points * 3 * 4);
-    m_sel = o; o += aligned(n * 4);
+    pts_a = o; o += round_up(n * HW * 3 * 4, kAlign);
+    pix = o; o += round_up(n * HW * 4, kAlign);
+    mind = o; o += round_up(n * HW * 4, kAlign);
+    count = o; o += round_up(n * 4, kAlign);
+    indices = o; o += round_up(n * n_points * 4, kAlign);
+    a = o; o += round_up(n * n_points * 3 * 4, kAlign);
+    b = o; o += round_up(n * n_points * 3 * 4, kAlign);
+    m_sel = o; o += round_up(n * 4, kAlign);
     total = o;
   }
 };

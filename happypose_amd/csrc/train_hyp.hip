@@ -23,6 +23,7 @@
 //   init_boxes_kernel  a thread is one row: identity rotation, z = (z_lo + z_hi) / 2, xy = ((box centre - cxcy) z) / fxfy in
 //                      float32 in the reference's order of operations; an id outside its table gives a NaN pose and reads row 0.
 #include "common.h"
+#include "philox.h"
 
 namespace hp {
 namespace {
@@ -30,20 +31,6 @@ namespace {
 #pragma clang fp contract(off)  // every product and sum below rounds once, in the order written
 
 constexpr int kThreads = 256;
-
-__device__ inline void philox_round(uint32_t c[4], uint32_t k0, uint32_t k1) {
-  const uint64_t p0 = (uint64_t)0xD2511F53u * c[0], p1 = (uint64_t)0xCD9E8D57u * c[2];
-  const uint32_t n0 = (uint32_t)(p1 >> 32) ^ c[1] ^ k0, n2 = (uint32_t)(p0 >> 32) ^ c[3] ^ k1;
-  c[0] = n0, c[1] = (uint32_t)p1, c[2] = n2, c[3] = (uint32_t)p0;
-}
-
-__device__ inline void philox4x32_10(uint32_t c[4], uint32_t k0, uint32_t k1) {
-#pragma unroll
-  for (int r = 0; r < 10; ++r) {
-    philox_round(c, k0, k1);
-    k0 += 0x9E3779B9u, k1 += 0xBB67AE85u;
-  }
-}
 
 struct NoiseStd {
   float euler_deg[3], trans[3];

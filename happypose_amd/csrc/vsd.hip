@@ -16,11 +16,11 @@
 // rows, which in an evaluation share the frame and mostly the ground-truth layer -- those two of a row's three reads are then
 // served from the L2 of the XCD instead of from memory.
 #include "common.h"
+#include "wave.h"
 
 namespace hp {
 namespace {
 
-constexpr int kWave = 64;
 constexpr int kThreads = 256;
 constexpr int kVec = 4;                                  // pixels per thread per step
 constexpr int kSteps = 4;                                // steps per workgroup: 12 independent 16-byte loads per thread
@@ -43,12 +43,6 @@ struct Params {
   float delta;
   float taus[kMaxTaus];
 };
-
-__device__ inline int wave_add(int v) {
-#pragma unroll
-  for (int off = kWave / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, kWave);
-  return v;
-}
 
 // a row whose ids leave their tables reads nothing and is answered with -1 / NaN by finish_kernel
 __device__ inline bool load_row(const Params& p, int row, int& e, int& g, int& f) {
@@ -138,12 +132,12 @@ __global__ void __launch_bounds__(kThreads) vsd_kernel(Params p, int32_t* __rest
   const int lane = threadIdx.x % kWave, wave = threadIdx.x / kWave;
 #pragma unroll
   for (int k = 0; k < kCounts; ++k) {
-    const int r = wave_add(cnt[k]);
+    const int r = wave_sum(cnt[k]);
     if (lane == 0) s_red[wave][k] = r;
   }
 #pragma unroll
   for (int t = 0; t < kMaxTaus; ++t) {
-    const int r = t < p.n_tau ? wave_add(cost[t]) : 0;  // n_tau is uniform
+    const int r = t < p.n_tau ? wave_sum(cost[t]) : 0;  // n_tau is uniform
     if (lane == 0) s_red[wave][kCounts + t] = r;
   }
   __syncthreads();
@@ -175,7 +169,6 @@ __global__ void __launch_bounds__(kWave) finish_kernel(Params p, int n_chunks, c
   }
 }
 
-inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
 inline int64_t chunks_of(int64_t P) { return (P + kChunk - 1) / kChunk; }
 
@@ -220,7 +213,7 @@ extern "C" int hp_vsd(int n_rows, const int32_t* d_est_layer, const int32_t* d_g
   hipStream_t st = (hipStream_t)stream;
   int32_t* partials = (int32_t*)d_workspace;
   const dim3 grid((unsigned)n_rows, (unsigned)chunks);
-  if (P % 4 == 0 && aligned16(d_depth_test) && aligned16(d_depth_layers))
+  if (P % 4 == 0 && aligned(d_depth_test, 16) && aligned(d_depth_layers, 16))
     hipLaunchKernelGGL(vsd_kernel<true>, grid, dim3(kThreads), 0, st, p, partials);
   else
     hipLaunchKernelGGL(vsd_kernel<false>, grid, dim3(kThreads), 0, st, p, partials);

@@ -78,6 +78,15 @@ def _check_ids(ids, n: int, what: str) -> None:
             raise IndexError(f"{what}: ids in [{lo}, {hi}] index a table of {n} rows")
 
 
+def _assert_ids(ids, n: int, what: str) -> None:
+    """The evaluation and detection kernels (``hp_vsd``, ``hp_det_iou``, the detector losses) REQUIRE ids inside their tables: ids that
+    still live on the host are checked here, before any launch.  An ``AssertionError``, unlike ``_check_ids``."""
+    t = torch.as_tensor(ids)
+    if t.device.type == "cpu" and t.numel():
+        lo, hi = int(t.min()), int(t.max())
+        assert 0 <= lo and hi < n, f"{what}: ids in [{lo}, {hi}] index a table of {n}"
+
+
 class MeshStore:
     """Device-resident object set: geometry/textures for the rasteriser and the padded
     mesh-point table for the projection kernels (``hp_mesh_store``)."""
@@ -1579,14 +1588,6 @@ def vsd_workspace_bytes(n_rows: int, h: int, w: int) -> int:
     return n
 
 
-def _vsd_ids(ids, n: int, what: str) -> None:
-    """``hp_vsd`` requires ids inside their tables: ids that still live on the host are checked here, before any launch."""
-    t = torch.as_tensor(ids)
-    if t.device.type == "cpu" and t.numel():
-        lo, hi = int(t.min()), int(t.max())
-        assert 0 <= lo and hi < n, f"{what}: ids in [{lo}, {hi}] index a table of {n}"
-
-
 def vsd_tables(est_layer, gt_layer, frame, diameter, depth_test: torch.Tensor, depth_layers: torch.Tensor, K: torch.Tensor,
                delta: float, taus, normalized_by_diameter: bool = True) -> Dict[str, torch.Tensor]:
     """``hp_vsd``: row ``r`` compares the depth renders ``depth_layers[est_layer[r]]`` and ``depth_layers[gt_layer[r]]``
@@ -1611,9 +1612,9 @@ def vsd_tables(est_layer, gt_layer, frame, diameter, depth_test: torch.Tensor, d
     assert 1 <= n_tau <= VSD_MAX_TAUS, f"vsd: 1 to {VSD_MAX_TAUS} taus"
     n = len(est_layer)
     assert len(gt_layer) == len(frame) == len(diameter) == n
-    _vsd_ids(est_layer, n_layers, "vsd: est_layer")
-    _vsd_ids(gt_layer, n_layers, "vsd: gt_layer")
-    _vsd_ids(frame, n_frames, "vsd: frame")
+    _assert_ids(est_layer, n_layers, "vsd: est_layer")
+    _assert_ids(gt_layer, n_layers, "vsd: gt_layer")
+    _assert_ids(frame, n_frames, "vsd: frame")
     est_layer, gt_layer, frame = (_i32(a, dev) for a in (est_layer, gt_layer, frame))
     diameter = _f32(torch.as_tensor(diameter), dev)
     depth_test, depth_layers, K = _f32(depth_test, dev), depth_layers.contiguous(), _f32(K, dev)
@@ -1657,14 +1658,6 @@ def mask_pack(masks: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return words, area
 
 
-def _det_ids(ids, n: int, what: str) -> None:
-    """The kernels require ids inside their tables: ids that still live on the host are checked here, before any launch."""
-    t = torch.as_tensor(ids)
-    if t.device.type == "cpu" and t.numel():
-        lo, hi = int(t.min()), int(t.max())
-        assert 0 <= lo and hi < n, f"{what}: ids in [{lo}, {hi}] index a table of {n}"
-
-
 def _packed(p, what: str):
     words, area = p
     assert words.dim() == 2 and words.dtype == torch.int64 and words.is_cuda and words.shape[1] >= 1, f"{what}: words [n, W64] int64 on the device"
@@ -1701,8 +1694,8 @@ def det_iou(pred_idx, gt_idx, boxes_pred: Optional[torch.Tensor] = None, boxes_g
         out["inter"] = torch.empty((n,), dtype=torch.int32, device=dev)
         out["union"] = torch.empty((n,), dtype=torch.int32, device=dev)
         out["mask_iou"] = torch.empty((n,), dtype=torch.float32, device=dev)
-    _det_ids(pred_idx, n_pred, "det_iou: pred_idx")
-    _det_ids(gt_idx, n_gt, "det_iou: gt_idx")
+    _assert_ids(pred_idx, n_pred, "det_iou: pred_idx")
+    _assert_ids(gt_idx, n_gt, "det_iou: gt_idx")
     if n == 0:
         return out
     pred_idx, gt_idx = _i32(pred_idx, dev), _i32(gt_idx, dev)
@@ -2301,7 +2294,7 @@ def seg_boxes(segmentation: torch.Tensor, ids, count=None) -> Tuple[torch.Tensor
 
 # ---- the detector's training targets and losses (csrc/det_losses.hip) --------------------------------------------------------------
 def _det_rows(what: str, image_of, n: int, n_images: int, dev) -> torch.Tensor:
-    _det_ids(image_of, n_images, f"{what}: image_of")
+    _assert_ids(image_of, n_images, f"{what}: image_of")
     image_of = _i32(image_of, dev)
     assert image_of.shape == (n,), f"{what}: image_of [n]"
     return image_of

@@ -203,16 +203,10 @@ int launch_conv_stem7_pool(const ConvArgs& a, int f16, hipStream_t stream);
 int conv_stem7_f16_krow(int cin_real);
 bool conv_igemm_split_pool_launchable(const ConvArgs& a, int cout_pad);
 int launch_conv_igemm_split_pool(const ConvArgs& a, hipStream_t stream);
-// plan-time choice between the split-fp16 kernel and the exact-fp32 ones for a 3x3 stride-1 layer
-inline bool conv_use_split(int algo, int H, int W, int cin, int cout) {
-  (void)H; (void)W; (void)cin; (void)cout;  // measured faster than Winograd on every WideResNet / ResNet-34 layer shape
-  return algo == HP_CONV_ALGO_SPLIT || algo == HP_CONV_ALGO_AUTO;
-}
-// which generic-kernel layers move to conv_igemm_split.hip: all of them (1x1 included)
-inline bool conv_use_igemm_split(int kh, int Kpad) {
-  (void)kh; (void)Kpad;
-  return true;
-}
+// does `algo` take the split-fp16 kernels?  The only algorithm question that does not depend on the layer: they measured faster
+// than Winograd on every WideResNet / ResNet-34 layer shape, and every generic-kernel layer (1x1 included) has a split-fp16
+// twin in conv_igemm_split.hip.  Everything else about the choice is net.cpp's choose_conv.
+inline bool conv_algo_uses_split(int algo) { return algo == HP_CONV_ALGO_SPLIT || algo == HP_CONV_ALGO_AUTO; }
 // hipGraph safety (hp_scratch_launches): does kernel `fn` use scratch?  (asked once per instantiation, where it opts in to its
 // LDS size); every launch of such a kernel is counted
 bool note_kernel(const void* fn);

@@ -41,6 +41,9 @@ struct DevBuf {
   }
 };
 
+// which weight sets a layer gets: conv_weight_sets() is the one statement of it
+struct WeightSets { bool split, isplit, wino, stem7, shortcut; };
+
 struct ConvLayer {
   std::string wname;       // e.g. "backbone.layer1.0.conv1.weight"
   std::string bn_after;    // BN folded into this conv ("" = none)
@@ -54,7 +57,7 @@ struct ConvLayer {
                    // extra work items of the block's 3x3 / stride-2 launch (ConvArgs::sc_w)
   DevBuf w, w_wino, w_split, w_isplit, bias, lut, pre_scale, pre_shift;  // w_isplit: hi/lo halves for conv_igemm_split.hip  // w_wino: Winograd-transformed weights (3x3 s1 layers)
                                                                // w_split: fp16 hi/lo halves (conv_split.hip)
-  bool wino_ok = false;  // eligible for w_wino (built on first use)
+  WeightSets sets{};       // what pack_conv built (sets.wino: eligible for w_wino, built on first use)
   int cout_pad = 0;        // weight rows / bias padded to whole 64-wide tiles
   float pre_smax = 1.f, pre_bmax = 0.f;  // bound of the BN + ReLU prologue: |x_act| <= pre_smax max|x| + pre_bmax (ConvArgs::amax_a / amax_b)
   int se = 0;              // the input is gated by the squeeze-excitation vector of this block (1x1 projections)
@@ -441,6 +444,141 @@ int build_graph_r50fpn(Net& n) {
   return HP_OK;
 }
 
+// ---- Choosing a conv's kernel: one description of a conv site, one statement of the weight sets a layer
+//      gets, one ladder.  The networks (forward_chunk) and the single-layer entry (hp_conv2d_nhwc) both go through them. ----
+struct ConvSite {
+  // the layer
+  int H = 0, W = 0, Cin = 0, cin_real = 0, Ho = 0, Wo = 0, Cout = 0, kh = 0, kw = 0, stride = 1, pad = 0;
+  int act = HP_ACT_NONE;
+  bool se_gated = false;  // the input is multiplied by a per-image gate (pre_scale alone)
+  bool prologue = false;  // BN + ReLU on the input (pre_scale and pre_shift)
+  bool residual = false, bias = false;
+  int cout_pad = 0, Kpad = 0, run_mode = 0;
+  // the two rules of the single-layer entry, which transforms a weight set per call ("where the entries differ")
+  bool isplit_beside_split = false;  // the igemm-split set exists for a layer that has the 3x3 split set too
+  bool wino_classic_only = false;    // Winograd for unpadded, non-swish, ungated layers only
+  // the weight sets that exist, the algorithm, the batch
+  bool has_split = false, has_isplit = false, has_wino = false, has_stem7 = false;
+  int algo = HP_CONV_ALGO_AUTO, batch = 1;
+  // what the neighbours allow
+  bool pool_follows = false;      // a max-pool op reads this map next (the fused stems write the pooled map instead)
+  bool dw_se_follow = false;      // a depthwise conv of this map and its squeeze-excitation follow, wired for the fused front
+  int dw_k = 0, dw_stride = 0, dw_Ho = 0, dw_Wo = 0;
+  bool shortcut_follows = false;  // op o+1 is the block's 1x1 / stride-2 shortcut and may ride (shortcut_may_ride)
+  bool per_launch = false, sync_ops = false, no_sc_fusion = false;  // diagnostics that keep every launch apart
+};
+
+// the site as the *_applicable / *_launchable predicates take it; they test the pointers and never read through them
+ConvArgs site_args(const ConvSite& s) {
+  static const float set = 0.f;
+  ConvArgs a{};
+  a.H = s.H; a.W = s.W; a.Cin = s.Cin; a.Ho = s.Ho; a.Wo = s.Wo; a.Cout = s.Cout; a.stride = s.stride; a.pad = s.pad;
+  a.Kpad = s.Kpad; a.ktiles = s.Kpad / 32; a.relu = s.act; a.M = (int64_t)s.batch * s.Ho * s.Wo;
+  a.pre_scale = s.prologue || s.se_gated ? &set : nullptr; a.pre_shift = s.prologue ? &set : nullptr;
+  a.residual = s.residual ? &set : nullptr; a.bias = s.bias ? &set : nullptr;
+  return a;
+}
+
+// Which weight sets a layer gets (batch independent): pack_conv builds them, ensure_wino_weights builds `wino` on first use,
+// hp_conv2d_nhwc transforms the one its launch needs per call.
+WeightSets conv_weight_sets(const ConvSite& s) {
+  const ConvArgs a = site_args(s);
+  const bool plain_act = s.act != HP_ACT_SWISH && !s.se_gated;
+  const bool classic = plain_act && s.cout_pad == s.Cout && s.Kpad == s.kh * s.kw * s.Cin;  // what the 3x3 kernels support
+  WeightSets r{};
+  r.split = plain_act && conv_split_applicable(a, s.kh, s.kw);  // fp16 hi / lo halves for conv_split.hip
+  r.isplit = (!r.split || s.isplit_beside_split) && s.Kpad % 32 == 0;  // ... for conv_igemm_split.hip: every other layer,
+                                                                        // swish layers and SE-gated projections included
+  r.wino = conv_wino_applicable(a, s.kh, s.kw) && (classic || !s.wino_classic_only);
+  r.stem7 = conv_stem7_applicable(s.kh, s.kw, s.stride, s.pad, s.Cin, s.Cout, s.act, 0) && !s.run_mode && !s.prologue;
+  // a 1x1 / stride-2 / pad-0 shortcut whose 3x3 / stride-2 / pad-1 twin the persistent stride-2 kernel would take
+  ConvArgs twin = a;
+  twin.pad = 1;
+  r.shortcut = s.kh == 1 && s.kw == 1 && s.stride == 2 && s.pad == 0 && !s.residual && conv_pp_s2_applicable(twin, 3, 3) &&
+               s.cout_pad == s.Cout && s.cin_real == s.Cin && plain_act;
+  return r;
+}
+
+enum WeightSet { W_PACKED, W_SPLIT, W_ISPLIT, W_WINO, W_STEM7 };
+struct ConvChoice {
+  int path = HP_PATH_GENERIC;
+  WeightSet w = W_PACKED;        // the set ConvArgs::w points at
+  int variant = 0;               // 128x128 tiles, or 128x64
+  bool pool_fused = false, front_fused = false, shortcut_rides = false;  // what the launch absorbs
+  bool materialised = true;      // the output map is written
+  bool tracks_amax = true;       // the launch goes through the shared epilogue (ConvArgs::amax_out)
+  bool status = false;           // split-fp16 arithmetic: the launch gets the non-finite guard word
+  // FLOPs the matrix cores execute (padded tiles / K included).  Split-fp16 launches: three fp16 MFMAs per product, and an
+  // fp16 MFMA FLOP occupies the pipe for 1/16 of an fp32 one, so it counts 1/16: mfma_flops / time / fp32 peak stays "how
+  // busy is the pipe".  sc_mfma_flops: the riding shortcut's share (accounted as a launch of its own).
+  double mfma_flops = 0.0, sc_mfma_flops = 0.0;
+};
+
+// The ladder.  Pure: launches nothing, reads no Net.
+ConvChoice choose_conv(const ConvSite& s) {
+  const ConvArgs a = site_args(s);
+  const bool split_algo = conv_algo_uses_split(s.algo);
+  const bool wino_algo = s.algo == HP_CONV_ALGO_AUTO || s.algo == HP_CONV_ALGO_WINOGRAD_1WAVE || s.algo == HP_CONV_ALGO_WINOGRAD;
+  ConvChoice c;
+  c.variant = s.cout_pad % 128 == 0 ? 0 : 1;
+  if (s.dw_se_follow && s.has_isplit && s.kh == 1 && s.act == HP_ACT_SWISH && !s.se_gated && !s.residual && !s.prologue && s.bias &&
+      split_algo && mbconv_front_applicable(s.Cin, s.Kpad, s.Cout, s.dw_k, s.dw_stride)) {
+    // MBConv front: expansion + depthwise (+ SE pooling sums) in one launch, the expanded tensor stays on the CU
+    c.path = HP_PATH_MBCONV_FRONT; c.w = W_ISPLIT; c.front_fused = true; c.status = true;
+    const int th = s.dw_stride == 1 ? 8 : 4, tw = s.dw_stride == 1 ? 16 : 8;
+    const int rows = (((th - 1) * s.dw_stride + s.dw_k) * ((tw - 1) * s.dw_stride + s.dw_k) + 31) / 32 * 32;
+    c.mfma_flops = 2.0 * (double)s.batch * mbconv_front_tiles(s.dw_Ho, s.dw_Wo, s.dw_stride) * rows * ((s.Cout + 31) / 32 * 32) * s.Kpad * 3.0 / 16.0;
+  } else if (split_algo && s.has_stem7 && s.pool_follows) {
+    // MegaPose stem + ReLU + max-pool in one launch, the input region of a pooled tile staged once per channel slab
+    c.path = HP_PATH_STEM7_POOL; c.w = W_STEM7; c.pool_fused = true; c.status = true;
+    const int sc = s.Cin % 8 == 0 ? 8 : 4, ks = (7 * sc + 15) / 16;
+    c.mfma_flops = 3.0 / 16.0 * 2.0 * (double)a.M * (256.0 / 192.0) * s.Cout * (s.Cin / sc) * 7.0 * ks * 16.0;
+  } else if (split_algo && s.has_split && conv_split_launchable(a)) {
+    // A down-sampling block's 1x1 / stride-2 shortcut runs as extra work items of the block's 3x3 / stride-2 launch
+    // (conv3x3s2_pp, ConvArgs::sc_w): as a launch of its own it sits on a floor of 20 - 30 us whatever the kernel
+    c.shortcut_rides = s.shortcut_follows && !s.no_sc_fusion && !s.per_launch && !s.sync_ops;
+    c.path = c.shortcut_rides ? HP_PATH_SPLIT3X3_SHORTCUT : HP_PATH_SPLIT3X3; c.w = W_SPLIT; c.status = true;
+    if (c.shortcut_rides) c.sc_mfma_flops = 3.0 * 2.0 * (double)((a.M + 255) / 256 * 256) * s.Cout * s.Cin / 16.0;
+    // whole 256- / 512-row tiles; 256-row tiles on the ping-pong kernel
+    const int64_t bm = (s.Cout % 128 == 0 || (s.stride == 1 && conv_pp_split_applicable(a, s.kh, s.kw))) ? 256 : 512;
+    c.mfma_flops = 3.0 * 2.0 * (double)((a.M + bm - 1) / bm * bm) * s.Cout * s.Kpad / 16.0;
+  } else if (wino_algo && s.has_wino && conv_wino_launchable(a)) {
+    // exact fp32: 16 multiplies per 2x2 output tile, cin and cout
+    c.path = HP_PATH_WINOGRAD; c.w = W_WINO; c.tracks_amax = false;
+    c.mfma_flops = 2.0 * 16.0 * (double)s.batch * ((s.Ho + 1) / 2) * ((s.Wo + 1) / 2) * s.Cin * s.Cout;
+  } else {
+    c.mfma_flops = 2.0 * (double)((a.M + 127) / 128 * 128) * s.cout_pad * s.Kpad;  // M x Cout x Kpad
+    if (split_algo && s.has_isplit && conv_igemm_split_launchable(a)) {
+      c.path = HP_PATH_IGEMM_SPLIT; c.w = W_ISPLIT; c.status = true;
+      if (s.pool_follows && conv_igemm_split_pool_launchable(a, s.cout_pad)) {
+        // stem + ReLU + 3x3/s2 max-pool in one launch: the conv map is never written
+        c.pool_fused = true;
+        if (conv_stem_split_applicable(a, s.kh, s.kw, s.run_mode)) {
+          c.path = HP_PATH_STEM_SPLIT_POOL;
+          c.mfma_flops *= 256.0 / 192.0;  // 256 GEMM rows per 6 x 32 conv pixels (7 x 33 computed, the rest padding)
+        } else {
+          c.path = HP_PATH_IGEMM_SPLIT_POOL;
+          c.mfma_flops *= 1.24;  // conv pixels under the tile borders are computed twice (7 x 17 per 6 x 16)
+        }
+      }
+      c.mfma_flops *= 3.0 / 16.0;
+    } else if (s.algo != HP_CONV_ALGO_IGEMM && s.act != HP_ACT_SWISH && !s.se_gated && conv_patch_applicable(a, s.kh, s.kw)) {
+      c.path = HP_PATH_PATCH;
+    }
+  }
+  if (c.pool_fused || c.front_fused) { c.materialised = false; c.tracks_amax = false; }
+  return c;
+}
+
+// the layer part of a network conv's site (the sets that exist, algorithm, batch and neighbours are the forward's to add)
+ConvSite layer_site(const ConvLayer& L) {
+  ConvSite s;
+  s.H = L.H; s.W = L.W; s.Cin = L.cin; s.cin_real = L.cin_real; s.Ho = L.Ho; s.Wo = L.Wo; s.Cout = L.cout; s.kh = L.kh; s.kw = L.kw;
+  s.stride = L.stride; s.pad = L.pad; s.act = L.relu; s.se_gated = L.se != 0; s.prologue = !L.bn_before.empty() && !L.se;
+  s.residual = L.res_buf >= 0; s.cout_pad = L.cout_pad; s.Kpad = L.Kpad; s.run_mode = L.run_mode;
+  return s;
+}
+
 int pack_conv(Net& n, ConvLayer& L) {
   const std::vector<float>* w;
   const int rows = L.cout_real ? L.cout_real : L.cout;
@@ -461,41 +599,31 @@ int pack_conv(Net& n, ConvLayer& L) {
         }
   }
   if ((rc = L.w.upload(packed.data(), packed.size() * 4))) return rc;
-  {
-    ConvArgs probe{};
-    probe.stride = L.stride; probe.pad = L.pad; probe.Cin = L.cin; probe.Cout = L.cout;
-    probe.H = L.H; probe.W = L.W; probe.Ho = L.Ho; probe.Wo = L.Wo;
-    // The Winograd weight set (exact-fp32 U = G g G^T) is LAZY: only eligibility is recorded here; ensure_wino_weights()
-    // transforms it the first time a forward's algorithm can reach it (the guard's exact-fp32 fallback,
-    // hp_net_set_conv_algo).  The default plan never touches it: hp_net_create used to spend 150 MB and 58 transform
-    // launches per WideResNet-34 on kernels that lost to the direct split kernels.
-    if (conv_wino_applicable(probe, L.kh, L.kw)) L.wino_ok = true;
-    if (conv_split_applicable(probe, L.kh, L.kw) && L.cout_pad == L.cout && L.relu != HP_ACT_SWISH && !L.se) {
-      if ((rc = L.w_split.alloc(conv_split_weight_bytes(L.cout, L.cin)))) return rc;
-      if ((rc = conv_split_transform_weights((const float*)L.w.p, L.w_split.p, L.cout, L.cin, L.Kpad, L.stride, nullptr))) return rc;
-      HP_CHECK_HIP(hipStreamSynchronize(nullptr));
-    } else if (L.Kpad % 32 == 0) {  // swish layers and the SE-gated projections too (gate applied while staging)
-      if ((rc = L.w_isplit.alloc(conv_igemm_split_weight_bytes(L.cout_pad, L.Kpad)))) return rc;
-      if ((rc = conv_igemm_split_transform_weights((const float*)L.w.p, L.w_isplit.p, L.cout_pad, L.Kpad, nullptr))) return rc;
-      HP_CHECK_HIP(hipStreamSynchronize(nullptr));
-    }
-    {  // a 1x1 / stride-2 / pad-0 shortcut whose 3x3 / stride-2 / pad-1 twin the persistent stride-2 kernel would take
-      ConvArgs twin = probe;
-      twin.pad = 1;
-      if (L.kh == 1 && L.kw == 1 && L.stride == 2 && L.pad == 0 && L.res_buf < 0 && conv_pp_s2_applicable(twin, 3, 3) && L.cout_pad == L.cout &&
-          L.cin_real == L.cin && L.relu != HP_ACT_SWISH && !L.se) {
-        std::vector<float> w33((size_t)L.cout * 9 * L.cin, 0.f);  // [cout][(kh, kw)][cin], centre tap = the shortcut
-        for (int o = 0; o < L.cout; ++o)
-          for (int ci = 0; ci < L.cin; ++ci) w33[((size_t)o * 9 + 4) * L.cin + ci] = packed[(size_t)o * L.Kpad + ci];
-        DevBuf tmp;
-        if ((rc = tmp.upload(w33.data(), w33.size() * 4))) return rc;
-        if ((rc = L.w_short.alloc(conv_split_weight_bytes(L.cout, L.cin)))) return rc;
-        if ((rc = conv_split_transform_weights((const float*)tmp.p, L.w_short.p, L.cout, L.cin, 9 * L.cin, 2, nullptr))) return rc;
-        HP_CHECK_HIP(hipStreamSynchronize(nullptr));
-      }
-    }
+  const WeightSets sets = L.sets = conv_weight_sets(layer_site(L));
+  // The Winograd weight set (exact-fp32 U = G g G^T) is LAZY: only eligibility is recorded here; ensure_wino_weights()
+  // transforms it the first time a forward's algorithm can reach it (the guard's exact-fp32 fallback,
+  // hp_net_set_conv_algo).  The default plan never touches it: hp_net_create used to spend 150 MB and 58 transform
+  // launches per WideResNet-34 on kernels that lost to the direct split kernels.
+  if (sets.split) {
+    if ((rc = L.w_split.alloc(conv_split_weight_bytes(L.cout, L.cin)))) return rc;
+    if ((rc = conv_split_transform_weights((const float*)L.w.p, L.w_split.p, L.cout, L.cin, L.Kpad, L.stride, nullptr))) return rc;
+    HP_CHECK_HIP(hipStreamSynchronize(nullptr));
+  } else if (sets.isplit) {
+    if ((rc = L.w_isplit.alloc(conv_igemm_split_weight_bytes(L.cout_pad, L.Kpad)))) return rc;
+    if ((rc = conv_igemm_split_transform_weights((const float*)L.w.p, L.w_isplit.p, L.cout_pad, L.Kpad, nullptr))) return rc;
+    HP_CHECK_HIP(hipStreamSynchronize(nullptr));
   }
-  if (conv_stem7_applicable(L.kh, L.kw, L.stride, L.pad, L.cin, L.cout, L.relu, 0) && !L.run_mode && L.bn_before.empty()) {
+  if (sets.shortcut) {
+    std::vector<float> w33((size_t)L.cout * 9 * L.cin, 0.f);  // [cout][(kh, kw)][cin], centre tap = the shortcut
+    for (int o = 0; o < L.cout; ++o)
+      for (int ci = 0; ci < L.cin; ++ci) w33[((size_t)o * 9 + 4) * L.cin + ci] = packed[(size_t)o * L.Kpad + ci];
+    DevBuf tmp;
+    if ((rc = tmp.upload(w33.data(), w33.size() * 4))) return rc;
+    if ((rc = L.w_short.alloc(conv_split_weight_bytes(L.cout, L.cin)))) return rc;
+    if ((rc = conv_split_transform_weights((const float*)tmp.p, L.w_short.p, L.cout, L.cin, 9 * L.cin, 2, nullptr))) return rc;
+    HP_CHECK_HIP(hipStreamSynchronize(nullptr));
+  }
+  if (sets.stem7) {
     std::vector<float> wf(numel);
     for (int o = 0; o < L.cout; ++o) {
       const float sc = scale.empty() ? 1.f : scale[o];
@@ -893,7 +1021,7 @@ static int ensure_wino_weights(hp_net* net, int algo, hipStream_t stream) {
   for (auto& Lp : net->convs) {
     ConvLayer& L = *Lp;
     // exact-fp32 set: the Winograd algorithms, and under AUTO the layers without split-fp16 weights
-    if (L.wino_ok && !L.w_wino.p && (exact || (algo == HP_CONV_ALGO_AUTO && !L.w_split.p))) {
+    if (L.sets.wino && !L.w_wino.p && (exact || (algo == HP_CONV_ALGO_AUTO && !L.sets.split))) {
       if ((rc = can_build())) return rc;
       if ((rc = L.w_wino.alloc(conv_wino_weight_floats(L.cout, L.cin) * 4))) return rc;
       if ((rc = conv_wino_transform_weights((const float*)L.w.p, (float*)L.w_wino.p, L.cout, L.cin, L.Kpad, stream))) return rc;
@@ -902,8 +1030,320 @@ static int ensure_wino_weights(hp_net* net, int algo, hipStream_t stream) {
   return HP_OK;
 }
 
-// d_x: fp32 input [batch][h][w][c_pad]; or (fp16 plan only) d_x16: fp16 input [batch][h][w][cin16 of the stem];
-// b0 = index of the chunk's first sample in the caller's batch (tap offsets; b0 == 0 starts the launch-path record)
+namespace hp {
+namespace {
+
+// One chunk of a forward: what the op bodies below share, and the state carried from op to op.
+struct Chunk {
+  Net& net;
+  const float* d_x;    // fp32 input [batch][h][w][c_pad]; or (fp16 plan only)
+  const void* d_x16;   // fp16 input [batch][h][w][cin16 of the stem]
+  int b0, batch;       // b0 = index of the chunk's first sample in the caller's batch (tap offsets; b0 == 0 starts the launch-path record)
+  float *d_pose, *d_logits, *d_features;
+  hipStream_t stream;
+  bool f16, sync_ops /* diagnostics: fault isolation */, per_launch, no_sc_fusion /* HP_NET_NO_SHORTCUT_FUSION=1: separate launches */;
+  int algo;
+  unsigned* amax_words;
+  bool pool_fused = false;   // the stem wrote the pooled map itself: skip the max-pool op that follows it
+  bool front_fused = false;  // the expansion conv ran the depthwise conv after it too (mbconv_front.hip): skip that op
+  int dw_partials = 0;       // > 0: the depthwise launch left this many pooling partials per image for the SE op after it
+  int sc_done = -1;          // op index of a shortcut the 3x3 op before it has already run
+  std::vector<int> buf_amax; // arena slot -> op whose launch tracked max|y| of what it holds (-1: unknown)
+  // profiling: events are recorded on the launch stream and only READ in hp_net_profile_collect
+  EventPair run{};
+  bool run_open = false;
+
+  int prof_begin(int conv) {
+    if (!net.profiling || run_open) return HP_OK;
+    if (!net.ev_pool.empty()) { run = net.ev_pool.back(); net.ev_pool.pop_back(); }
+    else { run = EventPair{}; HP_CHECK_HIP(hipEventCreate(&run.e0)); HP_CHECK_HIP(hipEventCreate(&run.e1)); }
+    run.flops = run.mfma_flops = 0.0; run.n = 0; run.conv = per_launch ? conv : -1;
+    HP_CHECK_HIP(hipEventRecord(run.e0, stream));
+    run_open = true;
+    return HP_OK;
+  }
+  void prof_add(double flops, double mfma_flops) { if (run_open) { run.flops += flops; run.mfma_flops += mfma_flops; ++run.n; } }
+  int prof_end(bool force) {
+    if (!run_open || !(force || per_launch)) return HP_OK;
+    HP_CHECK_HIP(hipEventRecord(run.e1, stream));
+    net.ev_pending.push_back(run);
+    run_open = false;
+    return HP_OK;
+  }
+  // host-side record of what this forward launched for op i (hp_net_op_info); a later chunk that differs marks it MIXED
+  void note(size_t i, int path, bool materialised = true) {
+    if (b0 == 0) { net.op_path[i] = path; net.op_mat[i] = materialised; return; }
+    if (net.op_path[i] != path) net.op_path[i] = HP_PATH_MIXED;
+    net.op_mat[i] = net.op_mat[i] && materialised;
+  }
+  int tap(size_t i, bool materialised) {  // copy op i's output map of this chunk to its tap
+    void* dst = net.taps[i];
+    if (!dst || !materialised) return HP_OK;
+    const Op& o = net.ops[i];
+    const size_t elem = f16 ? 2 : 4;
+    int slot = o.out_buf;
+    size_t per_sample = (size_t)o.Ho * o.Wo * o.C;
+    if (o.kind == OP_CONV) { const ConvLayer& L = *net.convs[o.conv]; slot = L.out_buf; per_sample = (size_t)L.Ho * L.Wo * L.cout; }
+    else if (o.kind == OP_DW) { const DwLayer& D = *net.dws[o.conv]; slot = D.out_buf; per_sample = (size_t)D.Ho * D.Wo * D.C; }
+    HP_CHECK_HIP(hipMemcpyAsync((char*)dst + (size_t)b0 * per_sample * elem, net.bufs[slot].p, (size_t)batch * per_sample * elem,
+                                hipMemcpyDeviceToDevice, stream));
+    return HP_OK;
+  }
+  unsigned* amax_of(size_t op) const { return amax_words + op * (size_t)kAmaxSlots * kAmaxStride; }
+  const Op* next_op(size_t oi) const { return oi + 1 < net.ops.size() ? &net.ops[oi + 1] : nullptr; }
+};
+
+// Every body: the launches of op oi of this chunk; `written` = the op's output map exists after its turn.
+
+int op_conv_f16(Chunk& c, size_t oi, bool& written) {
+  Net& net = c.net; const Op& op = net.ops[oi]; ConvLayer& L = *net.convs[op.conv]; int rc;
+  ConvArgsH a{};
+  a.x = (const _Float16*)(L.in_buf < 0 ? c.d_x16 : net.bufs[L.in_buf].p);
+  a.w = (const _Float16*)L.w16.p;
+  a.bias = (const float*)L.bias.p;
+  a.residual = L.res_buf < 0 ? nullptr : (const _Float16*)net.bufs[L.res_buf].p;
+  a.pre_scale = (const _Float16*)L.pre_scale16.p;
+  a.pre_shift = (const _Float16*)L.pre_shift16.p;
+  a.lut = (const int4*)L.lut16.p;
+  a.y = (_Float16*)net.bufs[L.out_buf].p;
+  a.M = (int64_t)c.batch * L.Ho * L.Wo;
+  a.H = L.H; a.W = L.W; a.Cin = L.cin16; a.Ho = L.Ho; a.Wo = L.Wo; a.Cout = L.cout;
+  a.stride = L.stride; a.pad = L.pad; a.Kpad = L.Kpad16; a.ktiles = L.Kpad16 / 64; a.relu = L.relu;
+  a.kh = L.kh; a.kw = L.kw;
+  a.no_tail_split = net.tail_split ? 0 : 1;
+  a.status = net.d_status;  // every fp16 launch that writes activations reports into the network's guard word
+  a.x_bytes = (int64_t)c.batch * L.H * L.W * L.cin16 * 2;
+  a.w_bytes = (int64_t)L.cout * L.Kpad16 * 2;
+  if ((rc = c.prof_begin(op.conv))) return rc;
+  const Op* next = c.next_op(oi);
+  if (L.w_stem7.p && next && next->kind == OP_MAXPOOL && next->in_buf == L.out_buf && next->H == L.Ho && next->W == L.Wo) {
+    // stem + ReLU + max-pool in one launch (conv_stem7.hip): the conv map is never written
+    ConvArgs s7{};
+    s7.x = (const float*)a.x; s7.w = (const float*)L.w_stem7.p; s7.bias = a.bias; s7.y = (float*)net.bufs[next->out_buf].p;
+    s7.M = a.M; s7.H = L.H; s7.W = L.W; s7.Cin = L.cin16; s7.Ho = L.Ho; s7.Wo = L.Wo; s7.Cout = L.cout; s7.relu = L.relu;
+    s7.Kpad = L.cin_real;  // selects the kernel the weights were packed for
+    s7.status = a.status;
+    if ((rc = launch_conv_stem7_pool(s7, 1, c.stream))) return rc;
+    c.pool_fused = true; written = false;
+    c.note(oi, HP_PATH_STEM7_POOL_F16, false);
+    c.prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, 2.0 * (double)a.M * (256.0 / 192.0) * L.cout * 7 * conv_stem7_f16_krow(L.cin_real));
+  } else {
+    if ((rc = launch_conv_f16(a, c.stream))) return rc;
+    c.note(oi, HP_PATH_CONV_F16);
+    c.prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, 2.0 * (double)((a.M + 127) / 128 * 128) * L.cout * L.Kpad16);
+  }
+  return c.prof_end(false);
+}
+
+// May op oi + 1 ride in the launch of op oi, as the 1x1 / stride-2 shortcut of the block whose 3x3 / stride-2 conv op oi is?
+// The structure only (the plans put the shortcut right behind the 3x3 op); the diagnostics and the launch limits are
+// choose_conv's.  B.w_short exists only where the persistent stride-2 kernel takes this geometry (conv_weight_sets).
+bool shortcut_may_ride(const Net& net, size_t oi) {
+  if (oi + 1 >= net.ops.size() || net.ops[oi + 1].kind != OP_CONV) return false;
+  const ConvLayer& A = *net.convs[net.ops[oi].conv];
+  const ConvLayer& B = *net.convs[net.ops[oi + 1].conv];
+  if (!B.w_short.p || !A.w_split.p || A.kh != 3 || A.kw != 3 || A.stride != 2 || A.pad != 1 || A.res_buf >= 0 || A.se) return false;
+  if (A.in_buf != B.in_buf || A.cin != B.cin || A.cout != B.cout || A.H != B.H || A.W != B.W || A.Ho != B.Ho || A.Wo != B.Wo) return false;
+  return A.bn_before == B.bn_before && A.out_buf != B.out_buf;  // one staging prologue serves both
+}
+
+int op_conv(Chunk& c, size_t oi, bool& written) {
+  Net& net = c.net;
+  const Op& op = net.ops[oi];
+  if ((int)oi == c.sc_done) {
+    c.sc_done = -1;  // this shortcut rode in the previous op's launch
+    c.note(oi, HP_PATH_RODE);
+    return HP_OK;
+  }
+  ConvLayer& L = *net.convs[op.conv];
+  int rc;
+  ConvArgs a{};
+  a.x = L.in_buf < 0 ? c.d_x : (const float*)net.bufs[L.in_buf].p;
+  a.bias = (const float*)L.bias.p;
+  a.residual = L.res_buf < 0 ? nullptr : (const float*)net.bufs[L.res_buf].p;
+  a.pre_scale = (const float*)L.pre_scale.p;
+  a.pre_shift = (const float*)L.pre_shift.p;
+  a.lut = (const int4*)L.lut.p;
+  a.y = (float*)net.bufs[L.out_buf].p;
+  a.M = (int64_t)c.batch * L.Ho * L.Wo;
+  a.H = L.H; a.W = L.W; a.Cin = L.cin; a.Ho = L.Ho; a.Wo = L.Wo; a.Cout = L.cout;
+  a.stride = L.stride; a.pad = L.pad; a.Kpad = L.Kpad; a.ktiles = L.Kpad / 32; a.relu = L.relu;
+  a.algo = c.algo; a.no_tail_split = net.tail_split ? 0 : 1;
+  if (c.amax_words) {
+    if (L.in_buf >= 0 && c.buf_amax[L.in_buf] >= 0 && !L.se) {
+      a.amax_in = c.amax_of(c.buf_amax[L.in_buf]);
+      a.amax_a = L.pre_scale.p ? L.pre_smax : 1.f; a.amax_b = L.pre_scale.p ? L.pre_bmax : 0.f;
+    }
+    a.amax_out = c.amax_of(oi);
+  }
+  if (L.se) { a.pre_scale = (const float*)net.se_gate.p; a.pre_shift = nullptr; }  // gate [batch][Cin]
+  if (c.sync_ops)
+    std::fprintf(stderr, "[hp net]   conv %s M=%lld H=%d W=%d Cin=%d Ho=%d Wo=%d Cout=%d pad=%d Kpad=%d act=%d se=%d in=%d out=%d res=%d x=%p y=%p r=%p\n",
+                 L.wname.c_str(), (long long)a.M, a.H, a.W, a.Cin, a.Ho, a.Wo, a.Cout, a.pad, a.Kpad, a.relu, L.se, L.in_buf,
+                 L.out_buf, L.res_buf, (const void*)a.x, (void*)a.y, (const void*)a.residual);
+  if ((rc = c.prof_begin(op.conv))) return rc;
+  // the site: the layer, the sets it has by now, and what its neighbours allow
+  ConvSite s = layer_site(L);
+  s.bias = a.bias != nullptr;
+  s.has_split = L.w_split.p != nullptr; s.has_isplit = L.w_isplit.p != nullptr; s.has_wino = L.w_wino.p != nullptr; s.has_stem7 = L.w_stem7.p != nullptr;
+  s.algo = c.algo; s.batch = c.batch;
+  const Op* next = c.next_op(oi);
+  s.pool_follows = next && next->kind == OP_MAXPOOL && next->in_buf == L.out_buf && next->H == L.Ho && next->W == L.Wo;
+  const DwLayer* dw = nullptr;
+  if (oi + 2 < net.ops.size() && next->kind == OP_DW && net.ops[oi + 2].kind == OP_SE) {
+    const DwLayer& D = *net.dws[next->conv];
+    if (D.in_buf == L.out_buf && D.C == L.cout && D.H == L.Ho && D.W == L.Wo && net.ses[net.ops[oi + 2].conv]->in_buf == D.out_buf) {
+      dw = &D;
+      s.dw_se_follow = true; s.dw_k = D.k; s.dw_stride = D.stride; s.dw_Ho = D.Ho; s.dw_Wo = D.Wo;
+    }
+  }
+  s.shortcut_follows = shortcut_may_ride(net, oi);
+  s.per_launch = c.per_launch; s.sync_ops = c.sync_ops; s.no_sc_fusion = c.no_sc_fusion;
+  const ConvChoice ch = choose_conv(s);
+
+  const void* const sets[] = {L.w.p, L.w_split.p, L.w_isplit.p, L.w_wino.p, L.w_stem7.p};  // by WeightSet
+  a.w = (const float*)sets[ch.w];
+  if (ch.status) a.status = net.d_status;
+  if (ch.pool_fused) a.y = (float*)net.bufs[next->out_buf].p;  // the pooled map: the conv map is never written
+  switch (ch.path) {
+    case HP_PATH_MBCONV_FRONT: {
+      FrontArgs f{};
+      f.x = a.x; f.w_split = a.w; f.bias_e = a.bias; f.w_dw = (const float*)dw->w.p; f.bias_d = (const float*)dw->bias.p;
+      f.y = (float*)net.bufs[dw->out_buf].p; f.pool_partial = (float*)net.se_partial.p; f.status = net.d_status;
+      f.n = c.batch; f.H = L.H; f.W = L.W; f.Cin = L.cin; f.Cexp = L.cout; f.Ho = dw->Ho; f.Wo = dw->Wo; f.k = dw->k;
+      f.stride = dw->stride; f.pad_t = f.pad_l = dw->pad; f.Kpad = L.Kpad; f.rows_pad = L.cout_pad;
+      rc = launch_mbconv_front(f, c.stream);
+      c.buf_amax[dw->out_buf] = -1;
+      c.dw_partials = mbconv_front_tiles(dw->Ho, dw->Wo, dw->stride);
+      break;
+    }
+    case HP_PATH_STEM7_POOL: rc = launch_conv_stem7_pool(a, 0, c.stream); break;
+    case HP_PATH_SPLIT3X3_SHORTCUT: {  // the block's shortcut as extra work items of this launch
+      const int sc_op = (int)oi + 1;
+      const ConvLayer& S = *net.convs[net.ops[sc_op].conv];
+      c.sc_done = sc_op;
+      a.sc_w = (const float*)S.w_short.p; a.sc_bias = (const float*)S.bias.p; a.sc_y = (float*)net.bufs[S.out_buf].p;
+      a.sc_relu = S.relu;
+      a.sc_amax_out = c.amax_words ? c.amax_of(sc_op) : nullptr;
+      if (S.out_buf >= 0) c.buf_amax[S.out_buf] = c.amax_words ? sc_op : -1;
+      c.prof_add(2.0 * (double)a.M * S.cout * S.cin_real, ch.sc_mfma_flops);
+    }
+      [[fallthrough]];
+    case HP_PATH_SPLIT3X3: rc = launch_conv_split(a, c.stream); break;
+    case HP_PATH_WINOGRAD: rc = launch_conv_wino(a, c.stream); break;
+    case HP_PATH_STEM_SPLIT_POOL: rc = launch_conv_stem_split_pool(a, c.stream); break;
+    case HP_PATH_IGEMM_SPLIT_POOL: rc = launch_conv_igemm_split_pool(a, c.stream); break;
+    case HP_PATH_IGEMM_SPLIT: rc = launch_conv_igemm_split(a, ch.variant, c.stream); break;
+    case HP_PATH_PATCH: rc = launch_conv_patch(a, ch.variant, c.stream); break;
+    default: rc = launch_conv(a, ch.variant, c.stream); break;
+  }
+  c.pool_fused = ch.pool_fused; c.front_fused = ch.front_fused; written = ch.materialised;
+  c.note(oi, ch.path, ch.materialised);
+  if (rc) return rc;
+  if (L.out_buf >= 0) c.buf_amax[L.out_buf] = c.amax_words && ch.tracks_amax ? (int)oi : -1;
+  if (ch.pool_fused && next->out_buf >= 0) c.buf_amax[next->out_buf] = -1;  // the fused stems write the pooled map untracked
+  c.prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, ch.mfma_flops);
+  return c.prof_end(false);
+}
+
+int op_dw(Chunk& c, size_t oi, bool&) {
+  Net& net = c.net; int rc;
+  if (c.front_fused) {
+    c.front_fused = false;  // the expansion's launch wrote this depthwise output (and the pooling partials) already
+    c.note(oi, HP_PATH_FUSED_AWAY);
+    return c.prof_end(true);
+  }
+  if ((rc = c.prof_end(true))) return rc;
+  const DwLayer& D = *net.dws[net.ops[oi].conv];
+  c.buf_amax[D.out_buf] = -1;  // the depthwise kernels do not track their range
+  DwArgs d{};
+  d.x = D.in_buf < 0 ? c.d_x : (const float*)net.bufs[D.in_buf].p; d.w = (const float*)D.w.p; d.bias = (const float*)D.bias.p;
+  d.y = (float*)net.bufs[D.out_buf].p;
+  d.n = c.batch; d.H = D.H; d.W = D.W; d.C = D.C; d.Ho = D.Ho; d.Wo = D.Wo; d.k = D.k; d.stride = D.stride;
+  d.pad_t = d.pad_l = D.pad;
+  // the squeeze-excitation that follows pools this output: let the depthwise launch sum what it stores
+  c.dw_partials = 0;
+  const Op* next = c.next_op(oi);
+  if (next && next->kind == OP_SE && net.ses[next->conv]->in_buf == D.out_buf && dwconv_pools(d) &&
+      dwconv_pool_strips(D.Ho, D.k, D.stride) <= 32) {
+    d.pool_partial = (float*)net.se_partial.p;
+    c.dw_partials = dwconv_pool_strips(D.Ho, D.k, D.stride);
+  }
+  if ((rc = launch_dwconv(d, c.stream))) return rc;
+  c.note(oi, HP_PATH_DWCONV);
+  return HP_OK;
+}
+
+int op_se(Chunk& c, size_t oi, bool& written) {
+  Net& net = c.net; int rc;
+  if ((rc = c.prof_end(true))) return rc;
+  const SeLayer& S = *net.ses[net.ops[oi].conv];
+  if ((rc = launch_se((const float*)net.bufs[S.in_buf].p, (float*)net.se_partial.p, (float*)net.se_pooled.p, (float*)net.se_sq.p,
+                      (float*)net.se_gate.p, (const float*)S.w1.p, (const float*)S.b1.p, (const float*)S.w2.p, (const float*)S.b2.p,
+                      c.batch, S.HW, S.C, S.Cse, c.dw_partials, c.stream)))
+    return rc;
+  c.dw_partials = 0; written = false;
+  c.note(oi, HP_PATH_SE, false);
+  return HP_OK;
+}
+
+int op_resize(Chunk& c, size_t oi, bool&) {
+  Net& net = c.net; const Op& op = net.ops[oi]; int rc;
+  c.buf_amax[op.out_buf] = -1;
+  if ((rc = c.prof_end(true))) return rc;
+  if ((rc = launch_resize_nearest((const float*)net.bufs[op.in_buf].p, (float*)net.bufs[op.out_buf].p, c.batch, op.H, op.W,
+                                  op.C, op.Ho, op.Wo, op.conv, c.stream)))
+    return rc;
+  c.note(oi, HP_PATH_RESIZE);
+  return HP_OK;
+}
+
+int op_maxpool(Chunk& c, size_t oi, bool&) {
+  Net& net = c.net; const Op& op = net.ops[oi]; int rc;
+  if (c.pool_fused) {
+    c.pool_fused = false;
+    c.note(oi, HP_PATH_FUSED_AWAY);
+    return c.prof_end(true);
+  }
+  if ((rc = c.prof_end(true))) return rc;
+  if (c.f16) {
+    if ((rc = launch_maxpool_f16(net.bufs[op.in_buf].p, net.bufs[op.out_buf].p, c.batch, op.H, op.W, op.C, op.Ho, op.Wo, c.stream)))
+      return rc;
+    c.note(oi, HP_PATH_MAXPOOL_F16);
+    return HP_OK;
+  }
+  c.buf_amax[op.out_buf] = c.buf_amax[op.in_buf];  // a max over windows cannot exceed the input's largest magnitude
+  if ((rc = launch_maxpool((const float*)net.bufs[op.in_buf].p, (float*)net.bufs[op.out_buf].p, c.batch, op.H, op.W, op.C, op.Ho,
+                           op.Wo, c.stream)))
+    return rc;
+  c.note(oi, HP_PATH_MAXPOOL);
+  return HP_OK;
+}
+
+int op_head(Chunk& c, size_t oi, bool& written) {
+  Net& net = c.net; const Op& op = net.ops[oi]; int rc;
+  if ((rc = c.prof_end(true))) return rc;
+  // (fp16 plan: the head reads halves that the last conv stored and reported on, and accumulates in fp32: no guard of its own)
+  HeadArgs h{};
+  h.x = net.bufs[op.in_buf].p; h.x_is_half = c.f16 ? 1 : 0; h.HW = op.H * op.W; h.C = op.C;
+  h.fc_w = (const float*)net.fc_w.p; h.fc_b = (const float*)net.fc_b.p;
+  h.pose_w = (const float*)net.pose_w.p; h.pose_b = (const float*)net.pose_b.p;
+  h.pose_dim = c.d_pose ? net.pose_dim : 0;
+  h.logit_w = (const float*)net.logit_w.p; h.logit_b = (const float*)net.logit_b.p;
+  h.n_logits = c.d_logits ? net.n_logits : 0;
+  h.pose_out = c.d_pose; h.logit_out = c.d_logits; h.features = c.d_features;
+  h.ws_pool = (float*)net.head_ws.p; h.ws_fc = h.ws_pool ? h.ws_pool + (size_t)net.max_batch * 512 : nullptr;
+  if ((rc = launch_head(h, c.batch, c.stream))) return rc;
+  if (net.pooled_out && h.ws_pool)
+    HP_CHECK_HIP(hipMemcpyAsync(net.pooled_out + (size_t)c.b0 * 512, h.ws_pool, (size_t)c.batch * 512 * 4, hipMemcpyDeviceToDevice, c.stream));
+  written = false;
+  c.note(oi, HP_PATH_HEAD, false);
+  return HP_OK;
+}
+
+}  // namespace
+}  // namespace hp
+
 static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b0, int batch, float* d_pose, float* d_logits,
                          float* d_features, hipStream_t stream) {
   int rc;
@@ -913,28 +1353,6 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
       return rc;
     d_x16 = net->x16.p;
   }
-  const bool sync_ops = dbg(DBG_NET_SYNC) != 0;  // diagnostics: fault isolation
-  const bool per_launch = dbg(DBG_PROFILE_LAYERS) != 0;
-  // profiling: events are recorded on the launch stream and only READ in hp_net_profile_collect
-  EventPair run{};
-  bool run_open = false;
-  auto prof_begin = [&](int conv) -> int {
-    if (!net->profiling || run_open) return HP_OK;
-    if (!net->ev_pool.empty()) { run = net->ev_pool.back(); net->ev_pool.pop_back(); }
-    else { run = EventPair{}; HP_CHECK_HIP(hipEventCreate(&run.e0)); HP_CHECK_HIP(hipEventCreate(&run.e1)); }
-    run.flops = run.mfma_flops = 0.0; run.n = 0; run.conv = per_launch ? conv : -1;
-    HP_CHECK_HIP(hipEventRecord(run.e0, stream));
-    run_open = true;
-    return HP_OK;
-  };
-  auto prof_add = [&](double flops, double mfma_flops) { if (run_open) { run.flops += flops; run.mfma_flops += mfma_flops; ++run.n; } };
-  auto prof_end = [&](bool force) -> int {
-    if (!run_open || !(force || per_launch)) return HP_OK;
-    HP_CHECK_HIP(hipEventRecord(run.e1, stream));
-    net->ev_pending.push_back(run);
-    run_open = false;
-    return HP_OK;
-  };
   // the guard of an EARLIER forward fired (read without synchronising): from now on exact-fp32 kernels only
   // (not while `stream` is capturing: the exact set may still have to be BUILT -- ensure_wino_weights allocates -- and a
   // capture must record the kernels of the signature it was started for; the flag is adopted by the next eager forward or
@@ -949,310 +1367,28 @@ static int forward_chunk(hp_net* net, const float* d_x, const void* d_x16, int b
   if (!f16 && (rc = ensure_wino_weights(net, net_algo, stream))) return rc;
   unsigned* const amax_words = (f16 || !net->act_scale) ? nullptr : (unsigned*)net->amax.p;
   if (amax_words && (rc = launch_zero_words(amax_words, ((int)net->ops.size() + 1) * kAmaxSlots * kAmaxStride, stream))) return rc;
-  std::vector<int> buf_amax(net->bufs.size(), -1);  // arena slot -> op whose launch tracked max|y| of what it holds (-1: unknown)
-  int op_index = 0;
-  bool pool_fused = false;  // the stem wrote the pooled map itself: skip the max-pool op that follows it
-  bool front_fused = false; // the expansion conv ran the depthwise conv after it too (mbconv_front.hip): skip that op
-  int dw_partials = 0;      // > 0: the depthwise launch left this many pooling partials per image for the SE op after it
-  // A down-sampling block's 1x1 / stride-2 shortcut runs as extra work items of the block's 3x3 / stride-2 launch (conv3x3s2_pp,
-  // ConvArgs::sc_w): as a launch of its own it sits on a floor of 20 - 30 us whatever the kernel.  The plans put the shortcut
-  // right behind the 3x3 op.  HP_NET_NO_SHORTCUT_FUSION=1 / per-layer profiling: separate launches.
-  const bool no_sc_fusion = dbg(DBG_NET_NO_SHORTCUT_FUSION) != 0;
-  int sc_done = -1;       // op index of a shortcut the 3x3 op before it has already run
-  auto sc_pair = [&](size_t o3, size_t o1) -> bool {  // may op o1 (shortcut) ride in the launch of op o3 (3x3 / stride 2)?
-    if (no_sc_fusion || per_launch || sync_ops || f16 || o3 >= net->ops.size() || o1 >= net->ops.size()) return false;
-    if (net->ops[o3].kind != OP_CONV || net->ops[o1].kind != OP_CONV) return false;
-    const ConvLayer& A = *net->convs[net->ops[o3].conv];
-    const ConvLayer& B = *net->convs[net->ops[o1].conv];
-    if (!B.w_short.p || !A.w_split.p || A.kh != 3 || A.kw != 3 || A.stride != 2 || A.pad != 1 || A.res_buf >= 0 || A.se) return false;
-    if (A.in_buf != B.in_buf || A.cin != B.cin || A.cout != B.cout || A.H != B.H || A.W != B.W || A.Ho != B.Ho || A.Wo != B.Wo) return false;
-    if (A.bn_before != B.bn_before || A.out_buf == B.out_buf) return false;  // one staging prologue serves both
-    ConvArgs t{};
-    t.stride = 2; t.pad = 1; t.Cin = A.cin; t.Cout = A.cout; t.H = A.H; t.W = A.W; t.Ho = A.Ho; t.Wo = A.Wo;
-    t.M = (int64_t)batch * A.Ho * A.Wo;
-    return conv_use_split(net_algo, A.H, A.W, A.cin, A.cout) && conv_split_launchable(t) && conv_pp_s2_applicable(t, 3, 3);
-  };
-  // host-side record of what this forward launched for op i (hp_net_op_info); a later chunk that differs marks it MIXED
-  auto note = [&](size_t i, int path, bool materialised = true) {
-    if (b0 == 0) { net->op_path[i] = path; net->op_mat[i] = materialised; return; }
-    if (net->op_path[i] != path) net->op_path[i] = HP_PATH_MIXED;
-    net->op_mat[i] = net->op_mat[i] && materialised;
-  };
-  const size_t elem = f16 ? 2 : 4;
-  auto tap = [&](size_t i, bool materialised) -> int {  // copy op i's output map of this chunk to its tap
-    void* dst = net->taps[i];
-    if (!dst || !materialised) return HP_OK;
-    const Op& o = net->ops[i];
-    int slot = o.out_buf;
-    size_t per_sample = (size_t)o.Ho * o.Wo * o.C;
-    if (o.kind == OP_CONV) { const ConvLayer& L = *net->convs[o.conv]; slot = L.out_buf; per_sample = (size_t)L.Ho * L.Wo * L.cout; }
-    else if (o.kind == OP_DW) { const DwLayer& D = *net->dws[o.conv]; slot = D.out_buf; per_sample = (size_t)D.Ho * D.Wo * D.C; }
-    HP_CHECK_HIP(hipMemcpyAsync((char*)dst + (size_t)b0 * per_sample * elem, net->bufs[slot].p, (size_t)batch * per_sample * elem,
-                                hipMemcpyDeviceToDevice, stream));
-    return HP_OK;
-  };
+  Chunk c{*net, d_x, d_x16, b0, batch, d_pose, d_logits, d_features, stream, f16, dbg(DBG_NET_SYNC) != 0,
+          dbg(DBG_PROFILE_LAYERS) != 0, dbg(DBG_NET_NO_SHORTCUT_FUSION) != 0, net_algo, amax_words};
+  c.buf_amax.assign(net->bufs.size(), -1);
   for (size_t oi = 0; oi < net->ops.size(); ++oi) {
     const Op& op = net->ops[oi];
-    bool written = true;  // this op's output map exists after its turn
-    if (sync_ops) {
+    bool written = true;
+    if (c.sync_ops) {
       HP_CHECK_HIP(hipDeviceSynchronize());
-      std::fprintf(stderr, "[hp net] op %d kind %d conv %d (everything before it has completed)\n", op_index, (int)op.kind, op.conv);
+      std::fprintf(stderr, "[hp net] op %d kind %d conv %d (everything before it has completed)\n", (int)oi, (int)op.kind, op.conv);
     }
-    ++op_index;
-    if (op.kind == OP_CONV && f16) {
-      ConvLayer& L = *net->convs[op.conv];
-      ConvArgsH a{};
-      a.x = (const _Float16*)(L.in_buf < 0 ? d_x16 : net->bufs[L.in_buf].p);
-      a.w = (const _Float16*)L.w16.p;
-      a.bias = (const float*)L.bias.p;
-      a.residual = L.res_buf < 0 ? nullptr : (const _Float16*)net->bufs[L.res_buf].p;
-      a.pre_scale = (const _Float16*)L.pre_scale16.p;
-      a.pre_shift = (const _Float16*)L.pre_shift16.p;
-      a.lut = (const int4*)L.lut16.p;
-      a.y = (_Float16*)net->bufs[L.out_buf].p;
-      a.M = (int64_t)batch * L.Ho * L.Wo;
-      a.H = L.H; a.W = L.W; a.Cin = L.cin16; a.Ho = L.Ho; a.Wo = L.Wo; a.Cout = L.cout;
-      a.stride = L.stride; a.pad = L.pad; a.Kpad = L.Kpad16; a.ktiles = L.Kpad16 / 64; a.relu = L.relu;
-      a.kh = L.kh; a.kw = L.kw;
-      a.no_tail_split = net->tail_split ? 0 : 1;
-      a.status = net->d_status;  // every fp16 launch that writes activations reports into the network's guard word
-      a.x_bytes = (int64_t)batch * L.H * L.W * L.cin16 * 2;
-      a.w_bytes = (int64_t)L.cout * L.Kpad16 * 2;
-      if ((rc = prof_begin(op.conv))) return rc;
-      const Op* next16 = op_index < (int)net->ops.size() ? &net->ops[op_index] : nullptr;
-      if (L.w_stem7.p && next16 && next16->kind == OP_MAXPOOL && next16->in_buf == L.out_buf && next16->H == L.Ho &&
-          next16->W == L.Wo) {
-        // stem + ReLU + max-pool in one launch (conv_stem7.hip): the conv map is never written
-        ConvArgs s7{};
-        s7.x = (const float*)a.x; s7.w = (const float*)L.w_stem7.p; s7.bias = a.bias; s7.y = (float*)net->bufs[next16->out_buf].p;
-        s7.M = a.M; s7.H = L.H; s7.W = L.W; s7.Cin = L.cin16; s7.Ho = L.Ho; s7.Wo = L.Wo; s7.Cout = L.cout; s7.relu = L.relu;
-        s7.Kpad = L.cin_real;  // selects the kernel the weights were packed for
-        s7.status = a.status;
-        if ((rc = launch_conv_stem7_pool(s7, 1, stream))) return rc;
-        pool_fused = true; written = false;
-        note(oi, HP_PATH_STEM7_POOL_F16, false);
-        prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, 2.0 * (double)a.M * (256.0 / 192.0) * L.cout * 7 * conv_stem7_f16_krow(L.cin_real));
-      } else {
-        if ((rc = launch_conv_f16(a, stream))) return rc;
-        note(oi, HP_PATH_CONV_F16);
-        prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, 2.0 * (double)((a.M + 127) / 128 * 128) * L.cout * L.Kpad16);
-      }
-      if ((rc = prof_end(false))) return rc;
-    } else if (op.kind == OP_CONV && (int)oi == sc_done) {
-      sc_done = -1;  // this shortcut rode in the previous op's launch
-      note(oi, HP_PATH_RODE);
-    } else if (op.kind == OP_CONV) {
-      ConvLayer& L = *net->convs[op.conv];
-      ConvArgs a{};
-      a.x = L.in_buf < 0 ? d_x : (const float*)net->bufs[L.in_buf].p;
-      a.w = (const float*)L.w.p;
-      a.bias = (const float*)L.bias.p;
-      a.residual = L.res_buf < 0 ? nullptr : (const float*)net->bufs[L.res_buf].p;
-      a.pre_scale = (const float*)L.pre_scale.p;
-      a.pre_shift = (const float*)L.pre_shift.p;
-      a.lut = (const int4*)L.lut.p;
-      a.y = (float*)net->bufs[L.out_buf].p;
-      a.M = (int64_t)batch * L.Ho * L.Wo;
-      a.H = L.H; a.W = L.W; a.Cin = L.cin; a.Ho = L.Ho; a.Wo = L.Wo; a.Cout = L.cout;
-      a.stride = L.stride; a.pad = L.pad; a.Kpad = L.Kpad; a.ktiles = L.Kpad / 32; a.relu = L.relu;
-      a.algo = net_algo; a.no_tail_split = net->tail_split ? 0 : 1;
-      if (amax_words) {
-        if (L.in_buf >= 0 && buf_amax[L.in_buf] >= 0 && !L.se) {
-          a.amax_in = amax_words + (size_t)buf_amax[L.in_buf] * kAmaxSlots * kAmaxStride;
-          a.amax_a = L.pre_scale.p ? L.pre_smax : 1.f; a.amax_b = L.pre_scale.p ? L.pre_bmax : 0.f;
-        }
-        a.amax_out = amax_words + oi * (size_t)kAmaxSlots * kAmaxStride;
-      }
-      bool tracks_amax = amax_words != nullptr;  // cleared below for the launches that do not go through the shared epilogue
-      if (L.se) { a.pre_scale = (const float*)net->se_gate.p; a.pre_shift = nullptr; }  // gate [batch][Cin]
-      const int variant = L.cout_pad % 128 == 0 ? 0 : 1;  // 128x128 tiles, or 128x64
-      if (sync_ops)
-        std::fprintf(stderr, "[hp net]   conv %s M=%lld H=%d W=%d Cin=%d Ho=%d Wo=%d Cout=%d pad=%d Kpad=%d act=%d se=%d in=%d out=%d res=%d x=%p y=%p r=%p\n",
-                     L.wname.c_str(), (long long)a.M, a.H, a.W, a.Cin, a.Ho, a.Wo, a.Cout, a.pad, a.Kpad, a.relu, L.se, L.in_buf,
-                     L.out_buf, L.res_buf, (const void*)a.x, (void*)a.y, (const void*)a.residual);
-      if ((rc = prof_begin(op.conv))) return rc;
-      double mfma_flops = 0.0;
-      const int algo = net_algo;
-      // FLOPs the matrix cores actually execute (padded tiles / K included): 16 multiplies per
-      // 2x2 output tile, cin and cout for the Winograd layers, M x Cout x Kpad otherwise
-      const bool wino_ok = algo == HP_CONV_ALGO_AUTO || algo == HP_CONV_ALGO_WINOGRAD_1WAVE || algo == HP_CONV_ALGO_WINOGRAD;
-      const Op* next7 = op_index < (int)net->ops.size() ? &net->ops[op_index] : nullptr;
-      // MBConv front: expansion + depthwise (+ SE pooling sums) in one launch, the expanded tensor stays on the CU
-      const DwLayer* fdw = nullptr;
-      if (oi + 2 < net->ops.size() && net->ops[oi + 1].kind == OP_DW && net->ops[oi + 2].kind == OP_SE && L.w_isplit.p && L.kh == 1 &&
-          L.relu == HP_ACT_SWISH && !L.se && L.res_buf < 0 && !a.pre_scale && conv_use_split(algo, L.H, L.W, L.cin, L.cout)) {
-        const DwLayer& D = *net->dws[net->ops[oi + 1].conv];
-        if (D.in_buf == L.out_buf && D.C == L.cout && D.H == L.Ho && D.W == L.Wo && a.bias && net->ses[net->ops[oi + 2].conv]->in_buf == D.out_buf &&
-            mbconv_front_applicable(L.cin, L.Kpad, L.cout, D.k, D.stride))
-          fdw = &D;
-      }
-      if (fdw) {
-        FrontArgs f{};
-        f.x = a.x; f.w_split = L.w_isplit.p; f.bias_e = a.bias; f.w_dw = (const float*)fdw->w.p; f.bias_d = (const float*)fdw->bias.p;
-        f.y = (float*)net->bufs[fdw->out_buf].p; f.pool_partial = (float*)net->se_partial.p; f.status = net->d_status;
-        f.n = batch; f.H = L.H; f.W = L.W; f.Cin = L.cin; f.Cexp = L.cout; f.Ho = fdw->Ho; f.Wo = fdw->Wo; f.k = fdw->k;
-        f.stride = fdw->stride; f.pad_t = f.pad_l = fdw->pad; f.Kpad = L.Kpad; f.rows_pad = L.cout_pad;
-        rc = launch_mbconv_front(f, stream);
-        front_fused = true; tracks_amax = false; written = false;
-        note(oi, HP_PATH_MBCONV_FRONT, false);
-        buf_amax[fdw->out_buf] = -1;
-        dw_partials = mbconv_front_tiles(fdw->Ho, fdw->Wo, fdw->stride);
-        const int th = fdw->stride == 1 ? 8 : 4, tw = fdw->stride == 1 ? 16 : 8;
-        const int rows = (((th - 1) * fdw->stride + fdw->k) * ((tw - 1) * fdw->stride + fdw->k) + 31) / 32 * 32;
-        mfma_flops = 2.0 * (double)batch * dw_partials * rows * ((L.cout + 31) / 32 * 32) * L.Kpad * 3.0 / 16.0;
-      } else
-      if (conv_use_split(algo, L.H, L.W, L.cin, L.cout) && L.w_stem7.p && next7 && next7->kind == OP_MAXPOOL &&
-          next7->in_buf == L.out_buf && next7->H == L.Ho && next7->W == L.Wo) {
-        // MegaPose stem + ReLU + max-pool in one launch, the input region of a pooled tile staged once per channel slab
-        a.w = (const float*)L.w_stem7.p;
-        a.y = (float*)net->bufs[next7->out_buf].p;
-        a.status = net->d_status;
-        rc = launch_conv_stem7_pool(a, 0, stream);
-        pool_fused = true; tracks_amax = false; written = false;
-        note(oi, HP_PATH_STEM7_POOL, false);
-        const int sc = L.cin % 8 == 0 ? 8 : 4, ks = (7 * sc + 15) / 16;
-        mfma_flops = 3.0 / 16.0 * 2.0 * (double)a.M * (256.0 / 192.0) * L.cout * (L.cin / sc) * 7.0 * ks * 16.0;
-      } else if (conv_use_split(algo, L.H, L.W, L.cin, L.cout) && L.w_split.p && conv_split_launchable(a)) {
-        a.w = (const float*)L.w_split.p;
-        a.status = net->d_status;
-        int sc_op = -1;  // the block's shortcut as extra work items of this launch
-        if (sc_pair(oi, oi + 1)) { sc_op = (int)oi + 1; sc_done = sc_op; }
-        if (sc_op >= 0) {
-          const ConvLayer& S = *net->convs[net->ops[sc_op].conv];
-          a.sc_w = (const float*)S.w_short.p; a.sc_bias = (const float*)S.bias.p; a.sc_y = (float*)net->bufs[S.out_buf].p;
-          a.sc_relu = S.relu;
-          a.sc_amax_out = amax_words ? amax_words + (size_t)sc_op * kAmaxSlots * kAmaxStride : nullptr;
-          if (S.out_buf >= 0) buf_amax[S.out_buf] = amax_words ? sc_op : -1;
-          prof_add(2.0 * (double)a.M * S.cout * S.cin_real, 3.0 * 2.0 * (double)((a.M + 255) / 256 * 256) * S.cout * S.cin / 16.0);
-        }
-        rc = launch_conv_split(a, stream);
-        note(oi, sc_op >= 0 ? HP_PATH_SPLIT3X3_SHORTCUT : HP_PATH_SPLIT3X3);
-        // three fp16 MFMAs per product over whole 256- / 512-row tiles; an fp16 MFMA FLOP occupies the matrix pipe for
-        // 1/16 of an fp32 one, so it is counted as 1/16: mfma_flops / time / fp32 peak stays "how busy is the pipe"
-        const int64_t bm = (L.cout % 128 == 0 || (L.stride == 1 && conv_pp_split_applicable(a, L.kh, L.kw))) ? 256 : 512;  // 256-row tiles on the ping-pong kernel
-        mfma_flops = 3.0 * 2.0 * (double)((a.M + bm - 1) / bm * bm) * L.cout * L.Kpad / 16.0;
-      } else if (wino_ok && L.w_wino.p && conv_wino_launchable(a)) {
-        a.w = (const float*)L.w_wino.p;
-        rc = launch_conv_wino(a, stream);
-        note(oi, HP_PATH_WINOGRAD);
-        tracks_amax = false;
-        mfma_flops = 2.0 * 16.0 * (double)batch * ((L.Ho + 1) / 2) * ((L.Wo + 1) / 2) * L.cin * L.cout;
-      } else {
-        mfma_flops = 2.0 * (double)((a.M + 127) / 128 * 128) * L.cout_pad * L.Kpad;
-        const Op* next = op_index < (int)net->ops.size() ? &net->ops[op_index] : nullptr;  // op_index already points past this op
-        if (conv_use_split(algo, L.H, L.W, L.cin, L.cout) && L.w_isplit.p && conv_igemm_split_launchable(a) &&
-            conv_use_igemm_split(L.kh, L.Kpad)) {
-          a.w = (const float*)L.w_isplit.p;
-          a.status = net->d_status;
-          if (next && next->kind == OP_MAXPOOL && next->in_buf == L.out_buf && next->H == L.Ho && next->W == L.Wo &&
-              conv_igemm_split_pool_launchable(a, L.cout_pad)) {
-            // stem + ReLU + 3x3/s2 max-pool in one launch: the conv map is never written
-            a.y = (float*)net->bufs[next->out_buf].p;
-            if (conv_stem_split_applicable(a, L.kh, L.kw, L.run_mode)) {
-              rc = launch_conv_stem_split_pool(a, stream);
-              note(oi, HP_PATH_STEM_SPLIT_POOL, false);
-              mfma_flops *= 256.0 / 192.0;  // 256 GEMM rows per 6 x 32 conv pixels (7 x 33 computed, the rest padding)
-            } else {
-              rc = launch_conv_igemm_split_pool(a, stream);
-              note(oi, HP_PATH_IGEMM_SPLIT_POOL, false);
-              mfma_flops *= 1.24;  // conv pixels under the tile borders are computed twice (7 x 17 per 6 x 16)
-            }
-            pool_fused = true; tracks_amax = false; written = false;
-          } else {
-            rc = launch_conv_igemm_split(a, variant, stream);
-            note(oi, HP_PATH_IGEMM_SPLIT);
-          }
-          mfma_flops *= 3.0 / 16.0;  // three fp16 MFMAs per product, 1/16 of the pipe time each
-        } else if (algo != HP_CONV_ALGO_IGEMM && a.relu != HP_ACT_SWISH && !L.se && conv_patch_applicable(a, L.kh, L.kw)) {
-          rc = launch_conv_patch(a, variant, stream);
-          note(oi, HP_PATH_PATCH);
-        } else {
-          rc = launch_conv(a, variant, stream);
-          note(oi, HP_PATH_GENERIC);
-        }
-      }
-      if (rc) return rc;
-      if (L.out_buf >= 0) buf_amax[L.out_buf] = tracks_amax ? (int)oi : -1;
-      if (pool_fused && next7 && next7->out_buf >= 0) buf_amax[next7->out_buf] = -1;  // the fused stems write the pooled map untracked
-      prof_add(2.0 * (double)a.M * L.cout * L.kh * L.kw * L.cin_real, mfma_flops);
-      if ((rc = prof_end(false))) return rc;
-    } else if (op.kind == OP_DW && front_fused) {
-      front_fused = false;  // the expansion's launch wrote this depthwise output (and the pooling partials) already
-      note(oi, HP_PATH_FUSED_AWAY);
-      if ((rc = prof_end(true))) return rc;
-    } else if (op.kind == OP_DW) {
-      if ((rc = prof_end(true))) return rc;
-      const DwLayer& D = *net->dws[op.conv];
-      buf_amax[D.out_buf] = -1;  // the depthwise kernels do not track their range
-      DwArgs d{};
-      d.x = D.in_buf < 0 ? d_x : (const float*)net->bufs[D.in_buf].p; d.w = (const float*)D.w.p; d.bias = (const float*)D.bias.p;
-      d.y = (float*)net->bufs[D.out_buf].p;
-      d.n = batch; d.H = D.H; d.W = D.W; d.C = D.C; d.Ho = D.Ho; d.Wo = D.Wo; d.k = D.k; d.stride = D.stride;
-      d.pad_t = d.pad_l = D.pad;
-      // the squeeze-excitation that follows pools this output: let the depthwise launch sum what it stores
-      dw_partials = 0;
-      if (oi + 1 < net->ops.size() && net->ops[oi + 1].kind == OP_SE && net->ses[net->ops[oi + 1].conv]->in_buf == D.out_buf &&
-          dwconv_pools(d) && dwconv_pool_strips(D.Ho, D.k, D.stride) <= 32) {
-        d.pool_partial = (float*)net->se_partial.p;
-        dw_partials = dwconv_pool_strips(D.Ho, D.k, D.stride);
-      }
-      if ((rc = launch_dwconv(d, stream))) return rc;
-      note(oi, HP_PATH_DWCONV);
-    } else if (op.kind == OP_SE) {
-      if ((rc = prof_end(true))) return rc;
-      const SeLayer& S = *net->ses[op.conv];
-      if ((rc = launch_se((const float*)net->bufs[S.in_buf].p, (float*)net->se_partial.p, (float*)net->se_pooled.p, (float*)net->se_sq.p,
-                          (float*)net->se_gate.p,
-                          (const float*)S.w1.p, (const float*)S.b1.p, (const float*)S.w2.p, (const float*)S.b2.p, batch, S.HW,
-                          S.C, S.Cse, dw_partials, stream)))
-        return rc;
-      dw_partials = 0; written = false;
-      note(oi, HP_PATH_SE, false);
-    } else if (op.kind == OP_RESIZE) {
-      buf_amax[op.out_buf] = -1;
-      if ((rc = prof_end(true))) return rc;
-      if ((rc = launch_resize_nearest((const float*)net->bufs[op.in_buf].p, (float*)net->bufs[op.out_buf].p, batch, op.H, op.W,
-                                      op.C, op.Ho, op.Wo, op.conv, stream)))
-        return rc;
-      note(oi, HP_PATH_RESIZE);
-    } else if (op.kind == OP_MAXPOOL && pool_fused) {
-      pool_fused = false;
-      note(oi, HP_PATH_FUSED_AWAY);
-      if ((rc = prof_end(true))) return rc;
-    } else if (op.kind == OP_MAXPOOL && f16) {
-      if ((rc = prof_end(true))) return rc;
-      if ((rc = launch_maxpool_f16(net->bufs[op.in_buf].p, net->bufs[op.out_buf].p, batch, op.H, op.W, op.C, op.Ho,
-                                   op.Wo, stream)))
-        return rc;
-      note(oi, HP_PATH_MAXPOOL_F16);
-    } else if (op.kind == OP_MAXPOOL) {
-      if ((rc = prof_end(true))) return rc;
-      buf_amax[op.out_buf] = buf_amax[op.in_buf];  // a max over windows cannot exceed the input's largest magnitude
-      if ((rc = launch_maxpool((const float*)net->bufs[op.in_buf].p, (float*)net->bufs[op.out_buf].p, batch,
-                               op.H, op.W, op.C, op.Ho, op.Wo, stream)))
-        return rc;
-      note(oi, HP_PATH_MAXPOOL);
-    } else {
-      if ((rc = prof_end(true))) return rc;
-      // (fp16 plan: the head reads halves that the last conv stored and reported on, and accumulates in fp32: no guard of its own)
-      HeadArgs h{};
-      h.x = net->bufs[op.in_buf].p; h.x_is_half = f16 ? 1 : 0; h.HW = op.H * op.W; h.C = op.C;
-      h.fc_w = (const float*)net->fc_w.p; h.fc_b = (const float*)net->fc_b.p;
-      h.pose_w = (const float*)net->pose_w.p; h.pose_b = (const float*)net->pose_b.p;
-      h.pose_dim = d_pose ? net->pose_dim : 0;
-      h.logit_w = (const float*)net->logit_w.p; h.logit_b = (const float*)net->logit_b.p;
-      h.n_logits = d_logits ? net->n_logits : 0;
-      h.pose_out = d_pose; h.logit_out = d_logits; h.features = d_features;
-      h.ws_pool = (float*)net->head_ws.p; h.ws_fc = h.ws_pool ? h.ws_pool + (size_t)net->max_batch * 512 : nullptr;
-      if ((rc = launch_head(h, batch, stream))) return rc;
-      if (net->pooled_out && h.ws_pool)
-        HP_CHECK_HIP(hipMemcpyAsync(net->pooled_out + (size_t)b0 * 512, h.ws_pool, (size_t)batch * 512 * 4, hipMemcpyDeviceToDevice, stream));
-      written = false;
-      note(oi, HP_PATH_HEAD, false);
+    switch (op.kind) {
+      case OP_CONV: rc = f16 ? op_conv_f16(c, oi, written) : op_conv(c, oi, written); break;
+      case OP_DW: rc = op_dw(c, oi, written); break;
+      case OP_SE: rc = op_se(c, oi, written); break;
+      case OP_RESIZE: rc = op_resize(c, oi, written); break;
+      case OP_MAXPOOL: rc = op_maxpool(c, oi, written); break;
+      default: rc = op_head(c, oi, written); break;
     }
-    if (!net->taps.empty() && (rc = tap(oi, written))) return rc;
+    if (rc) return rc;
+    if (!net->taps.empty() && (rc = c.tap(oi, written))) return rc;
   }
-  return prof_end(true);
+  return c.prof_end(true);
 }
 
 // taps copy into caller-owned memory at addresses that belong to one forward: not while `stream` captures
@@ -1528,7 +1664,49 @@ extern "C" int hp_net_set_profiling(hp_net* net, int enabled) {
 }
 
 
-// ---- single-layer entry for the kernel parity tests ------------------------------------
+// ---- single-layer entries for the kernel parity tests ------------------------------------
+namespace {
+
+// grow-only per-process scratch: the planner packs and transforms weights once at load time, these test entries on every call
+struct Scratch {
+  void* p = nullptr;
+  size_t bytes = 0;
+  int grow(size_t need) {
+    if (bytes >= need) return HP_OK;
+    if (p) (void)hipFree(p);
+    p = nullptr; bytes = 0;
+    HP_CHECK_HIP(hipMalloc(&p, need));
+    bytes = need;
+    return HP_OK;
+  }
+};
+
+// The gather table of a single-layer call: [Kpad / gran + extra] entries {offset, kh, kw, channel} over K in steps of `gran`
+// elements (4 floats, 8 halves), kh < 0 marking K padding.  It lives until the stream has consumed it: allocate, async copy,
+// free after sync is avoided by keeping a small per-process cache keyed on the geometry.
+struct LutCache {
+  std::map<std::string, int4*> map;
+  std::mutex mutex;
+  int get(int gran, int extra, int w, int cin, int kh, int kw, int Kreal, int Kpad, int4** d_lut) {  // with `mutex` held
+    int cur_dev = 0;
+    HP_CHECK_HIP(hipGetDevice(&cur_dev));
+    const std::string key = std::to_string(cur_dev) + "_" + std::to_string(w) + "_" + std::to_string(cin) + "_" + std::to_string(kh);
+    auto it = map.find(key);
+    if (it != map.end()) { *d_lut = it->second; return HP_OK; }
+    std::vector<int4> lut(Kpad / gran + extra, make_int4(0, -1, 0, 0));
+    for (int q = 0; q < Kreal / gran; ++q) {
+      const int k = gran * q, seg = k / cin, ch = k % cin, y = seg / kw, x = seg % kw;
+      lut[q] = make_int4((y * w + x) * cin + ch, y, x, ch);
+    }
+    HP_CHECK_HIP(hipMalloc((void**)d_lut, lut.size() * sizeof(int4)));
+    HP_CHECK_HIP(hipMemcpy(*d_lut, lut.data(), lut.size() * sizeof(int4), hipMemcpyHostToDevice));
+    map[key] = *d_lut;
+    return HP_OK;
+  }
+};
+
+}  // namespace
+
 extern "C" int hp_conv2d_nhwc(const float* d_x, int n, int h, int w, int cin, const float* d_w, int cout,
                               int kh, int kw, int stride, int pad, const float* d_bias,
                               const float* d_residual, const float* d_pre_scale,
@@ -1541,27 +1719,15 @@ extern "C" int hp_conv2d_nhwc(const float* d_x, int n, int h, int w, int cin, co
   HP_REQUIRE(relu >= HP_ACT_NONE && relu <= HP_ACT_SWISH, "hp_conv2d_nhwc: unknown activation");
   int rc = conv_setup_once();
   if (rc) return rc;
+  hipStream_t st = (hipStream_t)stream;
   const int Kreal = kh * kw * cin, Kpad = (Kreal + 31) / 32 * 32;
-  std::vector<int4> lut(Kpad / 4 + 16, make_int4(0, -1, 0, 0));
-  for (int q = 0; q < Kreal / 4; ++q) {
-    const int k = 4 * q, seg = k / cin, ch = k % cin, y = seg / kw, x = seg % kw;
-    lut[q] = make_int4((y * w + x) * cin + ch, y, x, ch);
-  }
-  // weights / bias padded to whole 64-wide tiles and to a multiple of 32 in K (the planner does
-  // this once at load time; this test entry on every call, into per-process scratch buffers)
+  // weights / bias padded to whole 64-wide tiles and to a multiple of 32 in K
   const int cout_pad = (cout + 63) / 64 * 64;
-  const bool padded = cout_pad != cout || Kpad != Kreal;
-  if (padded) {
-    static float* d_wp = nullptr;
-    static size_t wp_floats = 0;
+  if (cout_pad != cout || Kpad != Kreal) {
+    static Scratch wp;
     const size_t need = (size_t)cout_pad * Kpad + cout_pad;
-    if (wp_floats < need) {
-      if (d_wp) (void)hipFree(d_wp);
-      d_wp = nullptr; wp_floats = 0;
-      HP_CHECK_HIP(hipMalloc((void**)&d_wp, need * sizeof(float)));
-      wp_floats = need;
-    }
-    hipStream_t st = (hipStream_t)stream;
+    if ((rc = wp.grow(need * sizeof(float)))) return rc;
+    float* d_wp = (float*)wp.p;
     HP_CHECK_HIP(hipMemsetAsync(d_wp, 0, need * sizeof(float), st));
     HP_CHECK_HIP(hipMemcpy2DAsync(d_wp, (size_t)Kpad * 4, d_w, (size_t)Kreal * 4, (size_t)Kreal * 4, cout,
                                   hipMemcpyDeviceToDevice, st));
@@ -1569,23 +1735,10 @@ extern "C" int hp_conv2d_nhwc(const float* d_x, int n, int h, int w, int cin, co
     d_w = d_wp;
     if (d_bias) d_bias = d_wp + (size_t)cout_pad * Kpad;
   }
-  // the LUT lives until the stream has consumed it: allocate, async copy, free after sync is
-  // avoided by keeping a small per-process cache keyed on the geometry.
-  static std::map<std::string, int4*> cache;
-  static std::mutex cache_mutex;
-  std::lock_guard<std::mutex> cache_lock(cache_mutex);
-  int cur_dev = 0;
-  HP_CHECK_HIP(hipGetDevice(&cur_dev));
-  const std::string key = std::to_string(cur_dev) + "_" + std::to_string(w) + "_" + std::to_string(cin) + "_" + std::to_string(kh);
+  static LutCache cache;
+  std::lock_guard<std::mutex> cache_lock(cache.mutex);
   int4* d_lut = nullptr;
-  auto it = cache.find(key);
-  if (it == cache.end()) {
-    HP_CHECK_HIP(hipMalloc((void**)&d_lut, lut.size() * sizeof(int4)));
-    HP_CHECK_HIP(hipMemcpy(d_lut, lut.data(), lut.size() * sizeof(int4), hipMemcpyHostToDevice));
-    cache[key] = d_lut;
-  } else {
-    d_lut = it->second;
-  }
+  if ((rc = cache.get(4, 16, w, cin, kh, kw, Kreal, Kpad, &d_lut))) return rc;  // + 16: the kernel prefetches two K-tiles ahead
   ConvArgs a{};
   a.x = d_x; a.w = d_w; a.bias = d_bias; a.residual = d_residual; a.pre_scale = d_pre_scale;
   a.pre_shift = d_pre_shift; a.lut = d_lut; a.y = d_y;
@@ -1593,56 +1746,36 @@ extern "C" int hp_conv2d_nhwc(const float* d_x, int n, int h, int w, int cin, co
   a.Cout = cout; a.stride = stride; a.pad = pad; a.Kpad = Kpad; a.ktiles = Kpad / 32; a.relu = relu;
   a.M = (int64_t)n * a.Ho * a.Wo;
   a.algo = conv_layer_algo();
-  const bool classic = !padded && relu != HP_ACT_SWISH && (d_pre_shift || !d_pre_scale);  // what the 3x3 kernels support
-  const int algo = classic ? conv_layer_algo() : HP_CONV_ALGO_IGEMM;
-  if (conv_use_split(algo, h, w, cin, cout) && conv_split_applicable(a, kh, kw) && conv_split_launchable(a)) {
-    // test entry: the weights are split on every call into a per-process scratch buffer
-    static void* d_S = nullptr;
-    static size_t S_bytes = 0;
-    const size_t need_bytes = conv_split_weight_bytes(cout, cin);
-    if (S_bytes < need_bytes) {
-      if (d_S) (void)hipFree(d_S);
-      d_S = nullptr; S_bytes = 0;
-      HP_CHECK_HIP(hipMalloc(&d_S, need_bytes));
-      S_bytes = need_bytes;
-    }
-    if ((rc = conv_split_transform_weights(d_w, d_S, cout, cin, Kpad, stride, (hipStream_t)stream))) return rc;
-    a.w = (const float*)d_S;
-    return launch_conv_split(a, (hipStream_t)stream);
+  // the site of a layer without neighbours, its weight sets made on demand
+  ConvSite s;
+  s.H = h; s.W = w; s.Cin = s.cin_real = cin; s.Ho = a.Ho; s.Wo = a.Wo; s.Cout = cout; s.kh = kh; s.kw = kw; s.stride = stride; s.pad = pad;
+  s.act = relu; s.prologue = d_pre_scale && d_pre_shift; s.se_gated = d_pre_scale && !d_pre_shift;
+  s.residual = d_residual != nullptr; s.bias = d_bias != nullptr; s.cout_pad = cout_pad; s.Kpad = Kpad;
+  s.isplit_beside_split = s.wino_classic_only = true;
+  const WeightSets sets = conv_weight_sets(s);
+  s.has_split = sets.split; s.has_isplit = sets.isplit; s.has_wino = sets.wino;
+  s.algo = a.algo; s.batch = n;
+  const ConvChoice ch = choose_conv(s);
+  static Scratch ws[W_STEM7];  // one per transformed set
+  switch (ch.path) {
+    case HP_PATH_SPLIT3X3:
+      if ((rc = ws[W_SPLIT].grow(conv_split_weight_bytes(cout, cin)))) return rc;
+      if ((rc = conv_split_transform_weights(d_w, ws[W_SPLIT].p, cout, cin, Kpad, stride, st))) return rc;
+      a.w = (const float*)ws[W_SPLIT].p;
+      return launch_conv_split(a, st);
+    case HP_PATH_WINOGRAD:
+      if ((rc = ws[W_WINO].grow(conv_wino_weight_floats(cout, cin) * sizeof(float)))) return rc;
+      if ((rc = conv_wino_transform_weights(d_w, (float*)ws[W_WINO].p, cout, cin, Kpad, st))) return rc;
+      a.w = (const float*)ws[W_WINO].p;
+      return launch_conv_wino(a, st);
+    case HP_PATH_IGEMM_SPLIT:
+      if ((rc = ws[W_ISPLIT].grow(conv_igemm_split_weight_bytes(cout_pad, Kpad)))) return rc;
+      if ((rc = conv_igemm_split_transform_weights(d_w, ws[W_ISPLIT].p, cout_pad, Kpad, st))) return rc;
+      a.w = (const float*)ws[W_ISPLIT].p;
+      return launch_conv_igemm_split(a, ch.variant, st);
+    case HP_PATH_PATCH: return launch_conv_patch(a, ch.variant, st);
+    default: return launch_conv(a, ch.variant, st);
   }
-  if ((algo == HP_CONV_ALGO_AUTO || algo == HP_CONV_ALGO_WINOGRAD_1WAVE || algo == HP_CONV_ALGO_WINOGRAD) && conv_wino_applicable(a, kh, kw) && conv_wino_launchable(a)) {
-    // test entry: the weights are transformed on every call into a per-process scratch buffer
-    static float* d_U = nullptr;
-    static size_t U_floats = 0;
-    const size_t need_floats = conv_wino_weight_floats(cout, cin);
-    if (U_floats < need_floats) {
-      if (d_U) (void)hipFree(d_U);
-      d_U = nullptr; U_floats = 0;
-      HP_CHECK_HIP(hipMalloc((void**)&d_U, need_floats * sizeof(float)));
-      U_floats = need_floats;
-    }
-    if ((rc = conv_wino_transform_weights(d_w, d_U, cout, cin, Kpad, (hipStream_t)stream))) return rc;
-    a.w = d_U;
-    return launch_conv_wino(a, (hipStream_t)stream);
-  }
-  if (conv_use_split(conv_layer_algo(), h, w, cin, cout) && conv_igemm_split_launchable(a) && conv_use_igemm_split(kh, Kpad)) {
-    // test entry: the weights are split on every call into a per-process scratch buffer
-    static void* d_G = nullptr;
-    static size_t G_bytes = 0;
-    const size_t need_bytes = conv_igemm_split_weight_bytes(cout_pad, Kpad);
-    if (G_bytes < need_bytes) {
-      if (d_G) (void)hipFree(d_G);
-      d_G = nullptr; G_bytes = 0;
-      HP_CHECK_HIP(hipMalloc(&d_G, need_bytes));
-      G_bytes = need_bytes;
-    }
-    if ((rc = conv_igemm_split_transform_weights(d_w, d_G, cout_pad, Kpad, (hipStream_t)stream))) return rc;
-    a.w = (const float*)d_G;
-    return launch_conv_igemm_split(a, cout_pad % 128 == 0 ? 0 : 1, (hipStream_t)stream);
-  }
-  if (algo != HP_CONV_ALGO_IGEMM && conv_patch_applicable(a, kh, kw))
-    return launch_conv_patch(a, cout % 128 == 0 ? 0 : 1, (hipStream_t)stream);
-  return launch_conv(a, cout_pad % 128 == 0 ? 0 : 1, (hipStream_t)stream);
 }
 
 // ---- single-layer entry of the fp16 kernel for the parity tests (all tensors fp16 except bias) ----
@@ -1657,26 +1790,11 @@ extern "C" int hp_conv2d_nhwc_f16(const void* d_x, int n, int h, int w, int cin,
   HP_REQUIRE((d_pre_scale == nullptr) == (d_pre_shift == nullptr), "hp_conv2d_nhwc_f16: pre_scale/pre_shift must come together");
   const int Kreal = kh * kw * cin, Kpad = (Kreal + 63) / 64 * 64;
   HP_REQUIRE(Kreal == Kpad, "hp_conv2d_nhwc_f16: kh*kw*cin must be a multiple of 64 (weights are [cout][kh][kw][cin])");
-  std::vector<int4> lut(Kpad / 8);
-  for (int q = 0; q < Kpad / 8; ++q) {
-    const int k = 8 * q, seg = k / cin, ch = k % cin, y = seg / kw, x = seg % kw;
-    lut[q] = make_int4((y * w + x) * cin + ch, y, x, ch);
-  }
-  static std::map<std::string, int4*> cache;
-  static std::mutex cache_mutex;
-  std::lock_guard<std::mutex> cache_lock(cache_mutex);
-  int cur_dev = 0;
-  HP_CHECK_HIP(hipGetDevice(&cur_dev));
-  const std::string key = std::to_string(cur_dev) + "_" + std::to_string(w) + "_" + std::to_string(cin) + "_" + std::to_string(kh);
+  static LutCache cache;
+  std::lock_guard<std::mutex> cache_lock(cache.mutex);
   int4* d_lut = nullptr;
-  auto it = cache.find(key);
-  if (it == cache.end()) {
-    HP_CHECK_HIP(hipMalloc((void**)&d_lut, lut.size() * sizeof(int4)));
-    HP_CHECK_HIP(hipMemcpy(d_lut, lut.data(), lut.size() * sizeof(int4), hipMemcpyHostToDevice));
-    cache[key] = d_lut;
-  } else {
-    d_lut = it->second;
-  }
+  int rc = cache.get(8, 0, w, cin, kh, kw, Kreal, Kpad, &d_lut);
+  if (rc) return rc;
   ConvArgsH a{};
   a.x = (const _Float16*)d_x; a.w = (const _Float16*)d_w; a.bias = d_bias; a.residual = (const _Float16*)d_residual;
   a.pre_scale = (const _Float16*)d_pre_scale; a.pre_shift = (const _Float16*)d_pre_shift; a.lut = d_lut;

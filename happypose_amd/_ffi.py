@@ -218,6 +218,11 @@ _PROTOS = {
                                     c_f32p, c_f32p, C.c_void_p]),
     "hp_tco_init_from_boxes": (C.c_int, [C.c_int, c_f32p, C.c_int, c_i32p, c_f32p, C.c_int, c_i32p, C.c_float, C.c_float, c_f32p,
                                          C.c_void_p]),
+    "hp_views_sphere26": (C.c_int, [C.c_int, c_f32p, c_f32p, C.c_int, c_f32p, C.c_void_p]),
+    "hp_coarse_hypotheses": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_double, c_f32p, C.c_uint64, C.c_uint64, c_f32p, c_i32p, c_f32p,
+                                       C.c_void_p]),
+    "hp_loss_bce_logits": (C.c_int, [C.c_int64, c_f32p, c_f32p, C.c_float, c_f32p, C.c_void_p]),
+    "hp_loss_bce_logits_backward": (C.c_int, [C.c_int64, c_f32p, c_f32p, C.c_float, c_f32p, c_f32p, C.c_void_p]),
     "hp_det_assign_workspace_bytes": (C.c_int64, [C.c_int, C.c_int]),
     "hp_det_assign": (C.c_int, [C.c_int, c_f32p, c_i32p, C.c_int, c_f32p, C.c_int, c_i32p, C.c_float, C.c_float, C.c_int, c_i32p, c_f32p,
                                 C.c_void_p, C.c_int64, C.c_void_p]),

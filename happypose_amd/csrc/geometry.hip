@@ -4,6 +4,7 @@
 // TB/lib3d/multiview.py:189-190,212-222).  Here: one launch before the render
 // (hp_pose_prep) and one after the network (hp_pose_update).
 #include "common.h"
+#include "look_at.h"
 #include "wave.h"
 
 namespace hp {
@@ -30,24 +31,9 @@ __device__ __forceinline__ void normalize_T_dev(const float* Tin, float* T) {
   T[12] = 0.f; T[13] = 0.f; T[14] = 0.f; T[15] = 1.f;
 }
 
-// look-at pose (camera -> cam0, OpenCV axes) in double, as the reference's numpy/Panda path
-__device__ __forceinline__ void look_at_cv(const double* pos, const double* tgt, double* M /*[12]*/) {
-  double f[3] = {tgt[0] - pos[0], tgt[1] - pos[1], tgt[2] - pos[2]};
-  double nf = sqrt(f[0] * f[0] + f[1] * f[1] + f[2] * f[2]);
-  f[0] /= nf; f[1] /= nf; f[2] /= nf;
-  const double up[3] = {0.0, -1.0, 0.0};
-  double r[3] = {f[1] * up[2] - f[2] * up[1], f[2] * up[0] - f[0] * up[2], f[0] * up[1] - f[1] * up[0]};
-  double nr = sqrt(r[0] * r[0] + r[1] * r[1] + r[2] * r[2]);
-  r[0] /= nr; r[1] /= nr; r[2] /= nr;
-  double u[3] = {r[1] * f[2] - r[2] * f[1], r[2] * f[0] - r[0] * f[2], r[0] * f[1] - r[1] * f[0]};
-  // columns: right, -up', forward ; translation pos
-  M[0] = r[0]; M[1] = -u[0]; M[2] = f[0]; M[3] = pos[0];
-  M[4] = r[1]; M[5] = -u[1]; M[6] = f[1]; M[7] = pos[1];
-  M[8] = r[2]; M[9] = -u[2]; M[10] = f[2]; M[11] = pos[2];
-}
-
 // TCV_O = inv(TC0_CV) @ TCO for view v of "TCO+front_{1,3,5}views" (TB/lib3d/multiview.py:28-92,
-// 166-251; closed form derived in SURVEY.md A.9).  View 0 is the input pose itself.
+// 166-251; closed form derived in SURVEY.md A.9; the look-at and the fp32 tail are look_at.h's,
+// shared with train_hyp.hip).  View 0 is the input pose itself.
 __device__ __forceinline__ void view_pose(const float* T, int v, float* TV) {
   if (v == 0) {
 #pragma unroll
@@ -58,37 +44,11 @@ __device__ __forceinline__ void view_pose(const float* T, int v, float* TV) {
 #pragma unroll
   for (int k = 0; k < 12; ++k) fin &= isfinite(T[k]);
   double tcr[3] = {fin ? (double)T[3] : 0.0, fin ? (double)T[7] : 0.0, fin ? (double)T[11] : 0.0};
-  double radius = sqrt(tcr[0] * tcr[0] + tcr[1] * tcr[1] + tcr[2] * tcr[2]);
-  double M[12] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0};
-  if (radius > 0.0) {
-    double zero[3] = {0, 0, 0};
-    double base[12];
-    look_at_cv(zero, tcr, base);
-    // offsets in the Panda frame of `base`: x = right (cv x), y = forward (cv z), z = up (-cv y)
-    const int off[6][3] = {{0, 0, 0}, {0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 0, 1}, {0, 0, -1}};
-    double pos[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c)
-      pos[c] = radius * (off[v][0] * base[4 * c + 0] + off[v][1] * base[4 * c + 2] - off[v][2] * base[4 * c + 1]);
-    look_at_cv(pos, tcr, M);
-  }
-  float Mf[12];
-#pragma unroll
-  for (int k = 0; k < 12; ++k) Mf[k] = (float)M[k];
-  // invert_transform_matrices (TB/lib3d/transform_ops.py:59-67) in fp32, then @ TCO
-  float Ri[9] = {Mf[0], Mf[4], Mf[8], Mf[1], Mf[5], Mf[9], Mf[2], Mf[6], Mf[10]};
-  float ti[3];
-#pragma unroll
-  for (int r = 0; r < 3; ++r) ti[r] = -(Ri[3 * r] * Mf[3] + Ri[3 * r + 1] * Mf[7] + Ri[3 * r + 2] * Mf[11]);
-#pragma unroll
-  for (int r = 0; r < 3; ++r) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      float acc = Ri[3 * r] * T[c] + Ri[3 * r + 1] * T[4 + c] + Ri[3 * r + 2] * T[8 + c];
-      TV[4 * r + c] = acc + ti[r] * T[12 + c];
-    }
-  }
-  TV[12] = T[12]; TV[13] = T[13]; TV[14] = T[14]; TV[15] = T[15];
+  // offsets in the Panda frame of the re-aimed camera 0: x = right (cv x), y = forward (cv z), z = up (-cv y)
+  const int off[6][3] = {{0, 0, 0}, {0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 0, 1}, {0, 0, -1}};
+  double M[12];
+  look_at_view(tcr, off[v][0], off[v][1], off[v][2], false, M);
+  view_from_cam0(M, T, TV);
 }
 
 struct PrepArgs {

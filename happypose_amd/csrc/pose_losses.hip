@@ -1,6 +1,6 @@
-// The losses the pose networks are trained and validated on (loss_CO_symmetric, compute_ADD_L1_loss and the two disentangled
-// refiner losses), value and gradient: entry points, definitions and the reference lines they replace are in
-// include/happypose_amd.h.
+// The losses the pose networks are trained and validated on (loss_CO_symmetric, compute_ADD_L1_loss, the two disentangled
+// refiner losses and the rendered-views-logits loss), value and gradient: entry points, definitions and the reference lines they
+// replace are in include/happypose_amd.h.
 //
 // Three kernels, each instantiated for one term (the symmetric loss) and for three (orientation, xy, z of a refiner loss):
 //   terms_kernel     a workgroup is one (row, chunk of HP_POSE_LOSS_SYM_CHUNK symmetries).  Thread 0 builds the row's predicted poses
@@ -13,6 +13,8 @@
 //   backward_kernel  a workgroup is one row: for the chosen symmetry of each term the twelve sums of sign(d) (p | 1), then
 //                    thread 0 applies the analytic chain (Gram-Schmidt of the 6-D rotation, the image-space translation) and the
 //                    row's upstream gradient.
+// bce_logits_kernel (the coarse classifier's rendered-views-logits loss, value and gradient) is elementwise and described at its
+// definition.
 // The points are transformed in float32 (the arithmetic whose rounding the tests' sign-flip allowance describes); every SUM is
 // accumulated in double, per lane in point order, then over the wavefront by xor butterflies, then over the four wavefronts in
 // LDS in wavefront order.  No atomics: a row's outputs are a function of the row alone and the same bits in every run.
@@ -406,10 +408,57 @@ int forward(const char* what, int b, const LossArgs& a, float* d_loss, float* d_
   return check_launch(what);
 }
 
+// BCEWithLogitsLoss(reduction="none") of x = logit / temperature against y, the rendered-views-logits loss of the coarse
+// classifier: a thread is one element.  Everything is formed in double from the float32 inputs and rounded once.
+// forward: max(x, 0) - x y + log1p(exp(-|x|)); exp(-|x|) <= 1 cannot overflow, and beyond |x| ~ 37 the last term no longer
+// reaches the float32 result (the saturated branch).  backward: (sigmoid(x) - y) / temperature times the upstream gradient, with
+// sigmoid(x) = 1 / (1 + e) for x >= 0 and e / (1 + e) for x < 0, e = exp(-|x|).
+template <bool kBackward>
+__global__ void __launch_bounds__(kThreads) bce_logits_kernel(int64_t n, const float* __restrict__ logits, const float* __restrict__ y,
+                                                              double temperature, const float* __restrict__ grad_loss,
+                                                              float* __restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * kThreads + threadIdx.x;
+  if (i >= n) return;
+  const double x = (double)logits[i] / temperature, t = (double)y[i];
+  const double e = exp(-fabs(x));
+  if (kBackward) {
+    const double s = x >= 0.0 ? 1.0 / (1.0 + e) : e / (1.0 + e);
+    out[i] = (float)(((s - t) / temperature) * (double)grad_loss[i]);
+  } else {
+    out[i] = (float)(((x > 0.0 ? x : 0.0) - x * t) + log1p(e));
+  }
+}
+
 }  // namespace
 }  // namespace hp
 
 using namespace hp;
+
+extern "C" int hp_loss_bce_logits(int64_t n, const float* d_logits, const float* d_targets, float temperature, float* d_loss,
+                                  void* stream) {
+  HP_REQUIRE(n >= 0, "hp_loss_bce_logits: negative count");
+  HP_REQUIRE(temperature > 0.f && std::isfinite(temperature), "hp_loss_bce_logits: the temperature must be positive and finite");
+  if (n == 0) return HP_OK;
+  HP_REQUIRE(d_logits && d_targets && d_loss, "hp_loss_bce_logits: null pointer");
+  const int64_t n_blocks = (n + kThreads - 1) / kThreads;
+  HP_REQUIRE(n_blocks <= 0x7fffffff, "hp_loss_bce_logits: too many elements");
+  hipLaunchKernelGGL(bce_logits_kernel<false>, dim3((unsigned)n_blocks), dim3(kThreads), 0, (hipStream_t)stream, n, d_logits, d_targets,
+                     (double)temperature, (const float*)nullptr, d_loss);
+  return check_launch("hp_loss_bce_logits");
+}
+
+extern "C" int hp_loss_bce_logits_backward(int64_t n, const float* d_logits, const float* d_targets, float temperature,
+                                           const float* d_grad_loss, float* d_grad_logits, void* stream) {
+  HP_REQUIRE(n >= 0, "hp_loss_bce_logits_backward: negative count");
+  HP_REQUIRE(temperature > 0.f && std::isfinite(temperature), "hp_loss_bce_logits_backward: the temperature must be positive and finite");
+  if (n == 0) return HP_OK;
+  HP_REQUIRE(d_logits && d_targets && d_grad_loss && d_grad_logits, "hp_loss_bce_logits_backward: null pointer");
+  const int64_t n_blocks = (n + kThreads - 1) / kThreads;
+  HP_REQUIRE(n_blocks <= 0x7fffffff, "hp_loss_bce_logits_backward: too many elements");
+  hipLaunchKernelGGL(bce_logits_kernel<true>, dim3((unsigned)n_blocks), dim3(kThreads), 0, (hipStream_t)stream, n, d_logits, d_targets,
+                     (double)temperature, d_grad_loss, d_grad_logits);
+  return check_launch("hp_loss_bce_logits_backward");
+}
 
 extern "C" int64_t hp_pose_loss_workspace_bytes(int b, int n_sym) {
   if (b < 0 || n_sym < 1) return -1;

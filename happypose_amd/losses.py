@@ -4,7 +4,8 @@ Names and argument orders are the reference's (``TB/lib3d/cosypose_ops.py``, ``C
 ``TB/lib3d/mesh_losses.py``); definitions are in ``include/happypose_amd.h``.  This is the loss layer, not a trainer: what it
 gives is the value the reference logs as ``loss_TCO-iter=k`` (with ``-loss_orn``, ``-loss_xy``, ``-loss_z``) and its gradient
 with respect to the network's 9-D output (the refiner losses) or the upper 3 x 4 of ``TCO_pred`` (``loss_CO_symmetric``,
-``compute_ADD_L1_loss``).
+``compute_ADD_L1_loss``), and ``renderings_confidence_loss``, the logits loss of MegaPose's coarse classifier
+(``MP/training/megapose_forward_loss.py:224-239``), with its gradient with respect to the logits.
 
 Differences from the reference, all deliberate:
 
@@ -26,7 +27,7 @@ import torch
 from . import ops
 
 __all__ = ["l1", "l2", "loss_CO_symmetric", "compute_ADD_L1_loss", "loss_refiner_CO_disentangled",
-           "loss_refiner_CO_disentangled_reference_point"]
+           "loss_refiner_CO_disentangled_reference_point", "renderings_confidence_loss"]
 
 
 def l1(diff):
@@ -75,6 +76,21 @@ class _RefinerLoss(torch.autograd.Function):
         return grad.to(refiner_outputs.dtype), None, None, None, None, None
 
 
+class _BCELogitsLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, is_positive, temperature):
+        loss = ops.loss_bce_logits_forward(logits, is_positive, temperature)
+        ctx.save_for_backward(logits, is_positive)
+        ctx.temperature = float(temperature)
+        return loss
+
+    @staticmethod
+    def backward(ctx, grad_loss):
+        logits, is_positive = ctx.saved_tensors
+        grad = ops.loss_bce_logits_backward(logits, is_positive, ctx.temperature, grad_loss)
+        return grad.to(logits.dtype), None, None
+
+
 def loss_CO_symmetric(TCO_possible_gt: torch.Tensor, TCO_pred: torch.Tensor, points: torch.Tensor,
                       l1_or_l2=l1) -> Tuple[torch.Tensor, torch.Tensor]:
     """``(loss [B], TCO_assign [B, 4, 4])``: the smallest mean ``|TCO_pred p - TCO_possible_gt[:, s] p|`` over the symmetries
@@ -103,3 +119,11 @@ def loss_refiner_CO_disentangled_reference_point(TCO_possible_gt: torch.Tensor, 
     assert tCR is not None, "loss_refiner_CO_disentangled_reference_point: tCR [B, 3]"
     loss, parts = _RefinerLoss.apply(refiner_outputs, TCO_possible_gt, TCO_input, K_crop, points, tCR)
     return loss, {"loss_orn": parts[:, 0], "loss_xy": parts[:, 1], "loss_z": parts[:, 2], "loss": loss.detach()}
+
+
+def renderings_confidence_loss(logits: torch.Tensor, is_positive: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
+    """The coarse classifier's rendered-views-logits loss (``MP/training/megapose_forward_loss.py:224-239``):
+    ``nn.BCEWithLogitsLoss(reduction="none")(logits / temperature, is_positive)`` per element, in the stable form
+    ``max(x, 0) - x y + log1p(exp(-|x|))``; the result has the shape of ``logits``.  Differentiable with respect to ``logits``
+    only: ``(sigmoid(x) - y) / temperature``."""
+    return _BCELogitsLoss.apply(logits, is_positive, temperature)

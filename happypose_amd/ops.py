@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import functools
+import math
 import weakref
 from typing import Dict, List, Optional, Sequence, Tuple
 
@@ -1301,6 +1302,34 @@ def loss_refiner_backward(TCO_possible_gt: torch.Tensor, TCO_input: torch.Tensor
     return (grad, grad_parts) if return_parts else grad
 
 
+def _bce_tables(logits: torch.Tensor, targets: torch.Tensor, temperature: float, grad_loss: Optional[torch.Tensor] = None):
+    dev = _on_device("renderings_confidence_loss", logits=logits, is_positive=targets, grad_loss=grad_loss)
+    assert logits.shape == targets.shape, f"renderings_confidence_loss: logits {list(logits.shape)} and is_positive {list(targets.shape)}"
+    assert grad_loss is None or grad_loss.shape == logits.shape
+    assert float(temperature) > 0 and math.isfinite(float(temperature)), "renderings_confidence_loss: temperature > 0"
+    return dev, _f32(logits, dev), _f32(targets, dev), None if grad_loss is None else _f32(grad_loss, dev)
+
+
+def loss_bce_logits_forward(logits: torch.Tensor, targets: torch.Tensor, temperature: float = 1.0) -> torch.Tensor:
+    """``hp_loss_bce_logits``: per element ``BCEWithLogitsLoss(reduction="none")(logits / temperature, targets)``."""
+    dev, logits, targets, _ = _bce_tables(logits, targets, temperature)
+    loss = torch.empty(logits.shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_loss_bce_logits(logits.numel(), ptr(logits), ptr(targets), float(temperature), ptr(loss), stream_ptr(dev)),
+              "hp_loss_bce_logits")
+    return loss
+
+
+def loss_bce_logits_backward(logits: torch.Tensor, targets: torch.Tensor, temperature: float, grad_loss: torch.Tensor) -> torch.Tensor:
+    """``hp_loss_bce_logits_backward``: ``(sigmoid(logits / temperature) - targets) / temperature * grad_loss``."""
+    dev, logits, targets, grad_loss = _bce_tables(logits, targets, temperature, grad_loss)
+    grad = torch.empty(logits.shape, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_loss_bce_logits_backward(logits.numel(), ptr(logits), ptr(targets), float(temperature), ptr(grad_loss), ptr(grad),
+                                                stream_ptr(dev)), "hp_loss_bce_logits_backward")
+    return grad
+
+
 # ---- training hypotheses (csrc/train_hyp.hip) ------------------------------------------------------------------------------------
 def _on_device(what: str, **tensors) -> torch.device:
     """Every given tensor lives on one GPU (there is no CPU path): its device."""
@@ -1365,6 +1394,51 @@ def tco_init_from_boxes(boxes: torch.Tensor, K: torch.Tensor, z_range=(1.0, 1.0)
     return out
 
 
+SPHERE26_VIEWS, SPHERE26_CANDIDATES = 26, 104
+
+
+def views_sphere26(TCO: torch.Tensor, tCR: Optional[torch.Tensor] = None, inplane_rotations: bool = True) -> torch.Tensor:
+    """``hp_views_sphere26``: ``TCO [B, 4, 4]`` -> the candidate views of the coarse classifier ``[B, 104, 4, 4]`` (candidate
+    ``view * 4 + rot``), or ``[B, 26, 4, 4]`` without the in-plane rotations: ``make_TCO_multiview(TCO, tCR, "sphere_26views",
+    remove_TCO_rendering=True, views_inplane_rotations=True)``.  ``tCR [B, 3]`` defaults to the pose's translation.  Candidate 0
+    is camera 0 re-aimed at the reference point.  The header states the offsets' order and the degenerate look-at rule."""
+    dev = _on_device("views_sphere26", TCO=TCO, tCR=tCR)
+    assert TCO.dim() == 3 and TCO.shape[1:] == (4, 4), "views_sphere26: TCO [B, 4, 4]"
+    b = TCO.shape[0]
+    assert b * SPHERE26_CANDIDATES < 2 ** 31, "views_sphere26: too many poses"
+    TCO = _f32(TCO, dev)
+    if tCR is not None:
+        assert tCR.shape == (b, 3), "views_sphere26: tCR [B, 3]"
+        tCR = _f32(tCR, dev)
+    out = torch.empty(b, SPHERE26_CANDIDATES if inplane_rotations else SPHERE26_VIEWS, 4, 4, dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_views_sphere26(b, ptr(TCO), ptr(tCR), int(bool(inplane_rotations)), ptr(out), stream_ptr(dev)), "hp_views_sphere26")
+    return out
+
+
+def coarse_hypotheses(TCO: torch.Tensor, n_hypotheses: int, *, seed: int, row_offset: int = 0, n_rendered_views: int = 1,
+                      p_force_positive: float = 0.7) -> Tuple[torch.Tensor, torch.Tensor, torch.Tensor]:
+    """``hp_coarse_hypotheses``: per image ``n_hypotheses`` distinct candidates of :func:`views_sphere26` in one launch --
+    ``(hyp [B, n_hyp, 4, 4], view_ids [B, n_hyp] int32, is_positive [B, n_hyp] float32)``.  ``view_ids[b]`` are the first entries
+    of a uniform random permutation of ``0 .. 103`` drawn from ``(seed, row_offset + b)`` alone; where id 0 (the positive) is
+    absent it is forced into slot ``randint(n_rendered_views)`` with probability ``p_force_positive``.  Only the selected
+    candidates' poses are evaluated, with the bits :func:`views_sphere26` gives them.  The reference's ``np.random`` stream is
+    not reproduced; the header states the counter layout."""
+    dev = _on_device("coarse_hypotheses", TCO=TCO)
+    assert TCO.dim() == 3 and TCO.shape[1:] == (4, 4), "coarse_hypotheses: TCO [B, 4, 4]"
+    assert 0 <= seed < 2 ** 64 and 0 <= row_offset < 2 ** 64, "coarse_hypotheses: seed and row_offset are unsigned 64-bit integers"
+    b, n_hyp = TCO.shape[0], int(n_hypotheses)
+    assert b < 2 ** 31 // SPHERE26_CANDIDATES, "coarse_hypotheses: too many images"
+    TCO = _f32(TCO, dev)
+    hyp = torch.empty(b, max(n_hyp, 0), 4, 4, dtype=torch.float32, device=dev)
+    view_ids = torch.empty(b, max(n_hyp, 0), dtype=torch.int32, device=dev)
+    is_positive = torch.empty(b, max(n_hyp, 0), dtype=torch.float32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib().hp_coarse_hypotheses(b, n_hyp, int(n_rendered_views), float(p_force_positive), ptr(TCO), seed, row_offset, ptr(hyp),
+                                         ptr(view_ids), ptr(is_positive), stream_ptr(dev)), "hp_coarse_hypotheses")
+    return hyp, view_ids, is_positive
+
+
 # ---- head training (csrc/head_train.hip) -----------------------------------------------------------------------------------------
 def _f32_in(what: str, name: str, t: Optional[torch.Tensor], shape) -> None:
     if t is not None:
@@ -1372,18 +1446,22 @@ def _f32_in(what: str, name: str, t: Optional[torch.Tensor], shape) -> None:
             f"{what}: {name} must be contiguous float32 {list(shape)}, got {t.dtype} {list(t.shape)}"
 
 
-def head_backward(feat: torch.Tensor, d_pose: torch.Tensor, W: Optional[torch.Tensor] = None, *, d_logits: Optional[torch.Tensor] = None,
+def head_backward(feat: torch.Tensor, d_pose: Optional[torch.Tensor], W: Optional[torch.Tensor] = None, *,
+                  d_logits: Optional[torch.Tensor] = None,
                   n_logits: int = 0, w: Optional[torch.Tensor] = None, dW: Optional[torch.Tensor] = None,
                   db: Optional[torch.Tensor] = None, accumulate: bool = False, return_d_feat: bool = False):
     """``hp_head_backward``: ``feat [B, C]``, ``d_pose [B, pose_dim]`` and ``d_logits [B, n_logits]`` (None: zeros; ``n_logits``
     then gives the width) -> ``dW [O, C]``, ``db [O]`` with ``O = pose_dim + n_logits``, the pose rows first; optional row
-    weights ``w [B]``.  ``dW`` / ``db`` given: written in place, added to with ``accumulate``.  ``return_d_feat``: also
+    weights ``w [B]``.  ``d_pose`` None: a network without a pose head (``pose_dim == 0``, the coarse classifier), the logits rows
+    alone.  ``dW`` / ``db`` given: written in place, added to with ``accumulate``.  ``return_d_feat``: also
     ``d_feat [B, C] = (w d_out) @ W`` -- ``W [O, C]`` is needed for it alone.  Bit-identical from run to run (the header states the
     order of the sums)."""
     dev = _on_device("head_backward", feat=feat, d_pose=d_pose, d_logits=d_logits, w=w, W=W, dW=dW, db=db)
-    assert feat.dim() == 2 and d_pose.dim() == 2, "head_backward: feat [B, C], d_pose [B, pose_dim]"
+    assert feat.dim() == 2 and (d_pose is None or d_pose.dim() == 2), "head_backward: feat [B, C], d_pose [B, pose_dim]"
     B, Cf = feat.shape
-    pose_dim = d_pose.shape[1]
+    pose_dim = 0 if d_pose is None else d_pose.shape[1]
+    if pose_dim == 0:
+        d_pose = None  # nothing to read: the library takes a null pointer for an absent pose head
     if d_logits is not None:
         assert d_logits.dim() == 2, "head_backward: d_logits [B, n_logits]"
         n_logits = d_logits.shape[1]

@@ -4,8 +4,8 @@ output out.
 Names and argument orders are the reference's: ``h_pose`` (``CP/training/pose_forward_loss.py``), ``megapose_forward_loss``
 (``MP/training/megapose_forward_loss.py``), ``add_noise`` (``TB/lib3d/transform_ops.py:70-104``), ``TCO_init_from_boxes`` and
 ``TCO_init_from_boxes_zup_autodepth`` (``TB/lib3d/cosypose_ops.py:159-283``).  The hypotheses are made by ``csrc/train_hyp.hip``
-(``ops.pose_add_noise``, ``ops.tco_init_from_boxes``) and ``ops.tco_init_autodepth``, the predictor is one of this library's, the
-losses are ``happypose_amd.losses``: every input and every intermediate stays on the device.
+(``ops.pose_add_noise``, ``ops.tco_init_from_boxes``, ``ops.coarse_hypotheses``) and ``ops.tco_init_autodepth``, the predictor is one
+of this library's, the losses are ``happypose_amd.losses``: every input and every intermediate stays on the device.
 
 This is the step, not a trainer.  Each iteration's ``network_outputs["pose"]`` is marked ``requires_grad_()`` before the loss, so
 ``loss.backward()`` leaves ``dL/dpose`` in its ``.grad`` (``debug_dict["outputs"]["iteration=k"].network_outputs["pose"].grad``):
@@ -24,9 +24,13 @@ Differences from the reference, all deliberate:
   (``im_ids``) instead of gathered;
 * the auto-depth initialisations use the deterministic point subset of the estimators (``MeshStore.point_ids``) where the
   reference samples one at random;
-* not built: ``coarse_classif_multiview_paper`` (its ``sphere_26views`` cannot be pinned) and with it the
-  rendered-views-logits loss, ``n_pose_dims == 7`` (no quaternion loss kernel), ``random_ambient_light``, and the bokeh
-  visualisation (``make_visualization=True`` raises).
+* the coarse classifier's hypotheses (``coarse_classif_multiview_paper``): the reference builds the 104 ``sphere_26views``
+  candidates of every image on the host with Panda3D node paths and draws from ``np.random``; here ``ops.coarse_hypotheses``
+  draws and evaluates only the selected candidates in one launch.  The look-at is this library's closed form; where the up hint
+  is parallel to the viewing direction the header states this library's own rule (DESIGN.md 8);
+* not built: ``coarse_classif_multiview_SO3_grid`` (raises in the reference too), ``coarse_classif_multiview_paper`` without
+  ``cfg.predict_rendered_views_logits`` (the reference asserts the flag), ``n_pose_dims == 7`` (no quaternion loss kernel),
+  ``random_ambient_light``, and the bokeh visualisation (``make_visualization=True`` raises).
 """
 
 from __future__ import annotations
@@ -88,6 +92,9 @@ class TrainingConfig:
     loss_alpha_pose: float = 1.0
     predict_pose_update: bool = True
     predict_rendered_views_logits: bool = False
+    n_rendered_views: int = 1
+    renderings_logits_temperature: float = 1.0
+    loss_alpha_renderings_confidence: float = 1.0
 
 
 @dataclass
@@ -197,15 +204,31 @@ def _seed(seed: int, stream: int) -> int:
     return (int(seed) * 0x9E3779B97F4A7C15 + stream) & 0xFFFFFFFFFFFFFFFF
 
 
-def make_hypotheses(method: str, data, mesh_db, cfg, seed: int, *, store=None) -> torch.Tensor:
+def make_hypotheses(method: str, data, mesh_db, cfg, seed: int, *, store=None, return_labels: bool = False):
     """The initial hypotheses of a step, ``[B, n_hypotheses, 4, 4]`` on the device.  MegaPose's ``cfg.hypotheses_init_method``:
-    ``"coarse_z_up+auto-depth"`` (one hypothesis), ``"refiner_gt+noise"``; CosyPose's ``input_generator``: ``"fixed"``,
-    ``"gt+noise"``, ``"fixed+trans_noise"`` (one hypothesis each).  ``store``: the predictor's ``MeshStore``, for the auto-depth
-    methods.  ``mesh_db`` is not read by the methods that are built; it keeps the reference's place in the argument list."""
-    if method == "coarse_classif_multiview_paper":
-        raise NotImplementedError("coarse_classif_multiview_paper needs sphere_26views, which cannot be pinned (DESIGN.md 8)")
+    ``"coarse_z_up+auto-depth"`` (one hypothesis), ``"refiner_gt+noise"``, ``"coarse_classif_multiview_paper"``; CosyPose's
+    ``input_generator``: ``"fixed"``, ``"gt+noise"``, ``"fixed+trans_noise"`` (one hypothesis each).  ``store``: the predictor's
+    ``MeshStore``, for the auto-depth methods.  ``mesh_db`` is not read by the methods that are built; it keeps the reference's
+    place in the argument list.
+
+    ``"coarse_classif_multiview_paper"`` (the coarse classifier; the reference asserts ``cfg.predict_rendered_views_logits`` for
+    it): one noisy copy of each ground truth (``add_noise`` with ``cfg.init_euler_deg_std`` / ``cfg.init_trans_std``, key
+    ``_seed(seed, 1)``), then ``cfg.n_hypotheses`` of its 104 ``sphere_26views`` candidates (``ops.coarse_hypotheses``, key
+    ``_seed(seed, 4)``).  ``return_labels=True`` returns ``(hypotheses, is_positive [B, n_hyp] float32, view_ids [B, n_hyp]
+    int32)`` -- ``(hypotheses, None, None)`` for the other methods, whose return type without the keyword is unchanged."""
     if method == "coarse_classif_multiview_SO3_grid":
-        raise NotImplementedError
+        raise NotImplementedError  # as in the reference
+    if method == "coarse_classif_multiview_paper":
+        if not getattr(cfg, "predict_rendered_views_logits", False):
+            raise NotImplementedError("coarse_classif_multiview_paper draws the hypotheses of the rendered-views-logits loss: "
+                                      "set cfg.predict_rendered_views_logits = True (the reference asserts it)")
+        bt = data if isinstance(data, dict) and "B" in data else _batch(data, "make_hypotheses")
+        noisy = add_noise(bt["TCO"], cfg.init_euler_deg_std, cfg.init_trans_std, seed=_seed(seed, 1))
+        hyp, view_ids, is_positive = ops.coarse_hypotheses(noisy, int(cfg.n_hypotheses), seed=_seed(seed, 4),
+                                                           n_rendered_views=int(cfg.n_rendered_views))
+        return (hyp, is_positive, view_ids) if return_labels else hyp
+    if return_labels:
+        return make_hypotheses(method, data, mesh_db, cfg, seed, store=store), None, None
     if method not in MEGAPOSE_METHODS + COSYPOSE_METHODS:
         raise ValueError("Unknown hypotheses method", method)
     bt = data if isinstance(data, dict) and "B" in data else _batch(data, "make_hypotheses")
@@ -290,20 +313,31 @@ def megapose_forward_loss(model, cfg, data, meters, mesh_db, n_iterations: int, 
     ``time_render``, ``loss_TCO`` and ``loss_total`` and returns the loss as a device scalar; the gradient arrives at each
     iteration's ``network_outputs["pose"]``.  ``debug_dict`` receives the reference's ``outputs`` and ``time_render`` and, beyond
     them, ``hypotheses_TCO_init [B, n_hypotheses, 4, 4]``, ``points`` and ``TCO_possible_gt`` (per hypothesis row).  ``train``
-    is accepted and, as in the reference, not read."""
+    is accepted and, as in the reference, not read.
+
+    The coarse classifier (``cfg.predict_rendered_views_logits`` with ``"coarse_classif_multiview_paper"``, one iteration, one
+    rendered view): ``losses.renderings_confidence_loss`` of ``network_outputs["renderings_logits"]`` against the draw's
+    ``is_positive`` fills ``loss_renderings_confidence`` (after ``loss_TCO``, before ``loss_total``) and its gradient arrives at
+    ``network_outputs["renderings_logits"].grad``; ``debug_dict`` also receives ``is_hypothesis_positive`` and
+    ``views_permutation`` (the candidate ids).  With ``cfg.predict_pose_update = False`` there is no pose loss and no
+    ``loss_TCO*`` meter; with both flags both groups are filled."""
     if make_visualization:
         raise NotImplementedError("megapose_forward_loss: the bokeh visualisation is not built")
     if cfg.random_ambient_light:
         raise NotImplementedError("megapose_forward_loss: random_ambient_light is not built (set cfg.random_ambient_light = False)")
-    if cfg.predict_rendered_views_logits:
-        raise NotImplementedError("megapose_forward_loss: the rendered-views-logits loss needs coarse_classif_multiview_paper")
     method = cfg.hypotheses_init_method
     if method not in MEGAPOSE_METHODS and not method.startswith("coarse_classif_multiview"):
         raise ValueError(method)
+    logits_loss = bool(cfg.predict_rendered_views_logits)
+    if logits_loss:
+        if method != "coarse_classif_multiview_paper":
+            raise ValueError(f"megapose_forward_loss: the rendered-views-logits loss needs the labels of "
+                             f"coarse_classif_multiview_paper, not {method!r}")
+        assert cfg.n_rendered_views == 1 and n_iterations == 1  # as the reference asserts
     bt = _batch(data, "megapose_forward_loss")
     images = _images(bt, bool(getattr(model, "input_depth", False)))
     B, n_hyp = bt["B"], int(cfg.n_hypotheses)
-    hyp = make_hypotheses(method, bt, mesh_db, cfg, seed, store=getattr(model, "store", None))
+    hyp, is_positive, view_ids = make_hypotheses(method, bt, mesh_db, cfg, seed, store=getattr(model, "store", None), return_labels=True)
     outputs = _run_model(model, images, bt["K"], bt["labels"], hyp, n_iterations, random_ambient_light=False)
 
     points, TCO_possible_gt = _loss_tables(mesh_db, bt["labels"], bt["TCO"], int(cfg.n_points_loss), _seed(seed, 0))
@@ -330,11 +364,18 @@ def megapose_forward_loss(model, cfg, data, meters, mesh_db, n_iterations: int, 
         losses_pose = torch.stack(list_losses_pose).permute(1, 2, 0)
         loss_hypotheses = loss_hypotheses + cfg.loss_alpha_pose * losses_pose
         keyed.append(("loss_TCO", losses_pose.mean(dim=(-1, -2)).mean()))
+    if logits_loss:
+        logits = outputs["iteration=1"].network_outputs["renderings_logits"].requires_grad_()
+        assert logits.shape == (B * n_hyp, 1), "megapose_forward_loss: the model has no rendered-views-logits head of one view"
+        loss_renderings_confidence = losses.renderings_confidence_loss(logits.view(B, n_hyp), is_positive,
+                                                                       cfg.renderings_logits_temperature)
+        keyed.append(("loss_renderings_confidence", loss_renderings_confidence.mean()))
+        loss_hypotheses = loss_hypotheses + cfg.loss_alpha_renderings_confidence * loss_renderings_confidence[..., None]
     loss = loss_hypotheses.mean()
     keyed.append(("loss_total", loss))
 
-    # the reference's order: the iterations' meters, time_render, loss_TCO, loss_total
-    n_iter_keys = len(keyed) - (2 if cfg.predict_pose_update else 1)
+    # the reference's order: the iterations' meters, time_render, loss_TCO, loss_renderings_confidence, loss_total
+    n_iter_keys = len(keyed) - 1 - int(bool(cfg.predict_pose_update)) - int(logits_loss)
     values = torch.stack([v.detach().reshape(()) for _, v in keyed]).tolist()  # the step's one read-back
     for (key, _), v in list(zip(keyed, values))[:n_iter_keys]:
         meters[key].add(v)
@@ -343,6 +384,8 @@ def megapose_forward_loss(model, cfg, data, meters, mesh_db, n_iterations: int, 
         meters[key].add(v)
     if debug_dict is not None:
         debug_dict.update(outputs=outputs, time_render=time_render, hypotheses_TCO_init=hyp, points=points, TCO_possible_gt=TCO_possible_gt)
+        if logits_loss:
+            debug_dict.update(is_hypothesis_positive=is_positive, views_permutation=view_ids)
     return loss
 
 
@@ -506,8 +549,10 @@ class _WithFeatures:
 
 
 class HeadTrainer:
-    """Fine-tunes the linear heads of a pose network on its frozen backbone: the pose rows, the rendered-view logits rows (they
-    receive a zero gradient while no loss reads them) and, on the torchvision-ResNet path, the 512 x 512 ``fc`` in front of them.
+    """Fine-tunes the linear heads of a pose network on its frozen backbone: the pose rows, the rendered-view logits rows (their
+    gradient is ``renderings_logits.grad`` where the rendered-views-logits loss ran, zero otherwise) and, on the
+    torchvision-ResNet path, the 512 x 512 ``fc`` in front of them.  A network with a logits head and no pose head (the coarse
+    classifier, ``pose_dim == 0``) is trained on its logits rows alone.
 
     fp32 master copies of these tensors live in one flat device buffer ``p`` beside the gradient ``g`` and Adam's ``m`` / ``v``.
     :meth:`step` is ``megapose_forward_loss`` / ``h_pose``, ``loss.backward()`` (which leaves ``dL/dpose`` at every iteration's
@@ -524,8 +569,8 @@ class HeadTrainer:
         net = getattr(model, "backbone", None)
         if not isinstance(net, ops.Net):
             raise TypeError("HeadTrainer: the model must be a single-lane predictor of this library (model.backbone an ops.Net)")
-        if not net.pose_dim:
-            raise ValueError("HeadTrainer: the network has no pose head")
+        if not net.pose_dim and not net.n_logits:
+            raise ValueError("HeadTrainer: the network has neither a pose head nor a logits head")
         if optim_cfg is None:
             optim_cfg = HeadOptimConfig() if kind == "megapose" else HeadOptimConfig.cosypose()
         self.model, self.mesh_db, self.cfg, self.optim_cfg, self.kind = model, mesh_db, cfg, optim_cfg, kind
@@ -577,10 +622,16 @@ class HeadTrainer:
         # from here to the weight write: launches and device-to-device copies on the current stream only
         for k in range(n_iterations):
             out = dbg["outputs"][f"iteration={k + 1}"].network_outputs
-            d_pose = out["pose"].grad
-            assert d_pose is not None, "the loss did not reach this iteration's pose output"
-            res = ops.head_backward(out["features"], d_pose.contiguous(), self._W, n_logits=self.n_logits, dW=self._gW, db=self._gb,
-                                    accumulate=k > 0, return_d_feat=self.has_fc)
+            d_pose = out["pose"].grad if "pose" in out else None
+            d_logits = out["renderings_logits"].grad if "renderings_logits" in out else None
+            assert d_pose is not None or d_logits is not None, "the loss reached none of this iteration's network outputs"
+            assert d_pose is not None or not self.pose_dim or not getattr(self.cfg, "predict_pose_update", True), \
+                "the loss did not reach this iteration's pose output"
+            if d_pose is None and self.pose_dim:  # a pose head that no loss reads (cfg.predict_pose_update = False)
+                d_pose = torch.zeros((out["features"].shape[0], self.pose_dim), dtype=torch.float32, device=self.device)
+            res = ops.head_backward(out["features"], None if d_pose is None else d_pose.contiguous(), self._W,
+                                    d_logits=None if d_logits is None else d_logits.contiguous(), n_logits=self.n_logits,
+                                    dW=self._gW, db=self._gb, accumulate=k > 0, return_d_feat=self.has_fc)
             if self.has_fc:
                 ops.fc_backward(res[2], out["pooled"], dW=self.grads["backbone.fc.weight"], db=self.grads["backbone.fc.bias"],
                                 accumulate=k > 0)

@@ -868,6 +868,14 @@ int hp_loss_refiner_disentangled_backward(int b, int n_sym, int n_pts, const flo
                                           const float* d_refiner_outputs, const float* d_K_crop, const float* d_points,
                                           const float* d_tCR /* [b][3] or NULL */, const int32_t* d_sym_ids,
                                           const float* d_grad_loss, float* d_grad_outputs, float* d_grad_parts, void* stream);
+/* The rendered-views-logits loss of the coarse classifier (MP/training/megapose_forward_loss.py:224-239):
+ * nn.BCEWithLogitsLoss(reduction="none") of x = logit / temperature against the target y (0 / 1; any value in [0, 1] is accepted),
+ * per element:  loss = max(x, 0) - x y + log1p(exp(-|x|)),  d loss / d logit = (sigmoid(x) - y) / temperature, the backward call
+ * multiplies it by the element's upstream gradient d_grad_loss.  Evaluated in double from the float32 inputs and rounded once; no
+ * overflow for any finite logit.  n elements, n == 0 launches nothing; temperature <= 0 or not finite is HP_ERR_ARG. */
+int hp_loss_bce_logits(int64_t n, const float* d_logits, const float* d_targets, float temperature, float* d_loss, void* stream);
+int hp_loss_bce_logits_backward(int64_t n, const float* d_logits, const float* d_targets, float temperature, const float* d_grad_loss,
+                                float* d_grad_logits, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * Multi-object scenes:Panda3dSceneRenderer.render_scene(object_datas, camera_datas, light_datas, ...)
@@ -1260,6 +1268,49 @@ int hp_pose_add_noise(int n, int repeat, const float* d_TCO, const float* euler_
                       float* d_TCO_out, float* d_noise_out, void* stream);
 int hp_tco_init_from_boxes(int n, const float* d_boxes, int n_boxes, const int32_t* d_box_ids, const float* d_K, int n_images,
                            const int32_t* d_im_ids, float z_lo, float z_hi, float* d_TCO_out, void* stream);
+
+/* ------------------------------------------------------------------------------------
+ * The candidate views and the hypothesis draw of the coarse classifier's training step (csrc/train_hyp.hip):
+ * make_TCO_multiview(TCO, tCR, "sphere_26views", remove_TCO_rendering=True, views_inplane_rotations=True)
+ * (TB/lib3d/multiview.py:153-163, 224-251) and the per-image np.random.permutation / rand / randint of
+ * MP/training/megapose_forward_loss.py:126-141, which the reference runs on the host with Panda3D node paths.
+ *
+ * Candidates.  Pose d_TCO [b][16] (row-major 4 x 4), reference point d_tCR [b][3] in camera 0 (NULL: the pose's translation).
+ * The 26 views are cameras at  |tCR| (x, y, z)  in the Panda frame (x right, y forward, z up) of camera 0 re-aimed at tCR,
+ * (x, y, z) in the reference's loop order: y in (0, 1, 2) outermost, x in (0, -1, 1), z in (0, 1, -1) innermost, without (0, 1, 0)
+ * -- view 0 is (0, 0, 0), view 1 (0, 0, 1), ... view 9 (0, 1, 1) ... view 25 (1, 2, -1).  Each looks at tCR with camera 0's up as
+ * the hint: forward f exact, right = f x up / |f x up|, up' = right x f, evaluated in double in camera-0 OpenCV axes exactly as
+ * hp_pose_prep evaluates its front views (one shared device function); then TCV_O = invert_transform_matrices(TC0_CV) @ TCO in
+ * float32.  A pose with a non-finite entry in its upper 3 x 4 (or a non-finite d_tCR row), and |tCR| == 0, take the identity
+ * view, the rule of hp_pose_prep.
+ *   Degenerate look-at: where |f x up| < 1e-9 (f and up unit vectors) the hint defines no right vector and right is the right
+ *   axis of the re-aimed camera 0.  Offsets (0, 1, +-1) meet this when tCR_y is exactly 0; Panda3D's answer there is not
+ *   reproduced (like lookAt itself this is this library's definition, UNPINNED against the reference).
+ * In-plane rotations: candidate index = view * 4 + rot, rot = 0 .. 3; the rotation block is Rz(rot pi / 2) R with the exact
+ * entries 0 / +-1 (rot 1: rows (-r1, r0, r2); rot 2: (-r0, -r1, r2); rot 3: (r1, -r0, r2)), the translation is the view's.
+ * Candidate 0 is camera 0 re-aimed at the object without in-plane rotation: the classifier's positive.
+ * hp_views_sphere26 writes d_TCV_O [b][104][16], or [b][26][16] with inplane_rotations == 0 (bit for bit every fourth candidate).
+ *
+ * hp_coarse_hypotheses draws n_hyp (1 .. 104) of the 104 candidates per image and evaluates only those: d_hyp [b][n_hyp][16],
+ * d_view_ids [b][n_hyp] int32, d_is_positive [b][n_hyp] float32 (1 where the id is 0).  Image i draws from (seed, row_offset + i)
+ * alone: row = row_offset + i (64 bits), Philox4x32-10 (constants as for hp_mesh_sample_surface) with key
+ * (seed & 0xffffffff, seed >> 32) and counters (row & 0xffffffff, row >> 32, j, 0), j = 0 .. 26, giving words w[4 j + 0 .. 3].
+ *   ids     perm = (0, 1, .. 103); for i = 0 .. n_hyp - 1:  k = i + floor(w[i] (104 - i) / 2^32), swap perm[i], perm[k]
+ *           (integer arithmetic; the first n_hyp entries of a uniform random permutation).  Bias: k takes each of its 104 - i
+ *           values for floor or ceil of 2^32 / (104 - i) words, so its probability differs from 1 / (104 - i) by less than 2^-32
+ *           (relative: less than 104 x 2^-32 = 2.5e-8).
+ *   forced  where id 0 is absent and  w[104] > floor((1 - p_force_positive) 2^32)  (1 - p in binary64; u = w 2^-32 > 0.3 for the
+ *           reference's p = 0.7), slot floor(w[105] n_rendered_views / 2^32) becomes id 0: the reference's
+ *           randint(cfg.n_rendered_views), slot 0 for its one rendered view.  1 <= n_rendered_views <= n_hyp.
+ * The reference's global np.random stream is not reproduced.  No atomics: outputs are bit-identical from run to run, and
+ * d_hyp[i][h] holds the bits hp_views_sphere26 gives for candidate d_view_ids[i][h].  b == 0 returns HP_OK and launches nothing.
+ * ---------------------------------------------------------------------------------- */
+#define HP_SPHERE26_VIEWS 26
+#define HP_SPHERE26_CANDIDATES 104
+int hp_views_sphere26(int b, const float* d_TCO, const float* d_tCR /* [b][3] or NULL */, int inplane_rotations, float* d_TCV_O,
+                      void* stream);
+int hp_coarse_hypotheses(int b, int n_hyp, int n_rendered_views, double p_force_positive, const float* d_TCO, uint64_t seed,
+                         uint64_t row_offset, float* d_hyp, int32_t* d_view_ids, float* d_is_positive, void* stream);
 
 /* ------------------------------------------------------------------------------------
  * The detector's training targets and losses (csrc/det_losses.hip; the user-facing layer is happypose_amd/detection_losses.py and

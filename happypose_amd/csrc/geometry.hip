@@ -34,22 +34,36 @@ __device__ __forceinline__ void normalize_T_dev(const float* Tin, float* T) {
 // TCV_O = inv(TC0_CV) @ TCO for view v of "TCO+front_{1,3,5}views" (TB/lib3d/multiview.py:28-92,
 // 166-251; closed form derived in SURVEY.md A.9; the look-at and the fp32 tail are look_at.h's,
 // shared with train_hyp.hip).  View 0 is the input pose itself.
+// A pose with a non-finite entry among its 16 (the bottom row counts: without normalize it is the caller's) has the identity as the
+// camera of every look-at view, and the reference's matrix product, which adds every term, spreads such an entry over its column
+// of TCV_O (0 * NaN and 0 * inf are NaN), in view 0 too: a copy would keep the other rows.  Finite poses are not touched.
 __device__ __forceinline__ void view_pose(const float* T, int v, float* TV) {
-  if (v == 0) {
-#pragma unroll
-    for (int k = 0; k < 16; ++k) TV[k] = T[k];
-    return;
-  }
   bool fin = true;
 #pragma unroll
-  for (int k = 0; k < 12; ++k) fin &= isfinite(T[k]);
-  double tcr[3] = {fin ? (double)T[3] : 0.0, fin ? (double)T[7] : 0.0, fin ? (double)T[11] : 0.0};
+  for (int k = 0; k < 16; ++k) fin &= isfinite(T[k]);
+  if (v == 0 || !fin) {
+#pragma unroll
+    for (int k = 0; k < 16; ++k) TV[k] = T[k];
+    if (!fin) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (isfinite(T[c]) && isfinite(T[4 + c]) && isfinite(T[8 + c]) && isfinite(T[12 + c])) continue;
+#pragma unroll
+        for (int r = 0; r < 4; ++r) TV[4 * r + c] = __builtin_nanf("");
+      }
+    }
+    return;
+  }
+  double tcr[3] = {(double)T[3], (double)T[7], (double)T[11]};
   // offsets in the Panda frame of the re-aimed camera 0: x = right (cv x), y = forward (cv z), z = up (-cv y)
   const int off[6][3] = {{0, 0, 0}, {0, 0, 0}, {1, 0, 0}, {-1, 0, 0}, {0, 0, 1}, {0, 0, -1}};
   double M[12];
   look_at_view(tcr, off[v][0], off[v][1], off[v][2], false, M);
   view_from_cam0(M, T, TV);
 }
+
+// max that keeps a NaN, as the reference's torch.max does (fmaxf drops it); on other operands it is fmaxf bit for bit
+__device__ __forceinline__ float max_nan(float a, float b) { return (a != a || b != b) ? __builtin_nanf("") : fmaxf(a, b); }
 
 struct PrepArgs {
   const float* points; int n_pad;
@@ -66,6 +80,7 @@ struct PrepArgs {
 
 __global__ __launch_bounds__(kT) void pose_prep_kernel(PrepArgs a) {
   __shared__ float red[4][4];
+  __shared__ int red_nan[4];
   const int nvt = a.n_views + a.skip_tco;  // evaluated views: the rendered ones (+ the identity view when it is not rendered)
   const int i = blockIdx.x / nvt, v = blockIdx.x % nvt;
   const int slot = v - a.skip_tco;         // position among the rendered views, -1: the unrendered identity view
@@ -110,34 +125,45 @@ __global__ __launch_bounds__(kT) void pose_prep_kernel(PrepArgs a) {
   const int npts = v == 0 ? a.n_main : a.n_extra;
   const float* pts = a.points + (int64_t)(bad_id ? 0 : ob_id) * a.n_pad * 3;
   float x1 = INFINITY, y1 = INFINITY, x2 = -INFINITY, y2 = -INFINITY;
+  // fminf / fmaxf drop a NaN where the reference's min / max keep it (a non-finite pose, a degenerate look-at): bit 0 = a NaN
+  // among the u, bit 1 = among the w, and the boxes, the crop and its K follow as NaN
+  int nan_seen = 0;
   for (int j = tid; j < npts; j += kT) {
     const float* p = pts + 3 * (int64_t)ids[j];
     float su = fmaf(P[2], p[2], fmaf(P[1], p[1], P[0] * p[0])) + P[3];
     float sv = fmaf(P[6], p[2], fmaf(P[5], p[1], P[4] * p[0])) + P[7];
     float sz = fmaf(P[10], p[2], fmaf(P[9], p[1], P[8] * p[0])) + P[11];
-    sz = fmaxf(0.1f, sz);  // project_points_robust z clamp (:53-54)
+    sz = max_nan(0.1f, sz);  // project_points_robust z clamp (:53-54)
     float u = su / sz, w = sv / sz;
+    nan_seen |= (u != u ? 1 : 0) | (w != w ? 2 : 0);
     x1 = fminf(x1, u); x2 = fmaxf(x2, u); y1 = fminf(y1, w); y2 = fmaxf(y2, w);
   }
   x1 = wave_min(x1); y1 = wave_min(y1); x2 = wave_max(x2); y2 = wave_max(y2);
-  if ((tid & 63) == 0) { red[tid >> 6][0] = x1; red[tid >> 6][1] = y1; red[tid >> 6][2] = x2; red[tid >> 6][3] = y2; }
+  nan_seen = (__any(nan_seen & 1) ? 1 : 0) | (__any(nan_seen & 2) ? 2 : 0);
+  if ((tid & 63) == 0) {
+    red[tid >> 6][0] = x1; red[tid >> 6][1] = y1; red[tid >> 6][2] = x2; red[tid >> 6][3] = y2;
+    red_nan[tid >> 6] = nan_seen;
+  }
   __syncthreads();
   if (tid != 0) return;
 #pragma unroll
   for (int wv = 1; wv < 4; ++wv) {
     x1 = fminf(x1, red[wv][0]); y1 = fminf(y1, red[wv][1]);
     x2 = fmaxf(x2, red[wv][2]); y2 = fmaxf(y2, red[wv][3]);
+    nan_seen |= red_nan[wv];
   }
+  if (nan_seen & 1) x1 = x2 = __builtin_nanf("");
+  if (nan_seen & 2) y1 = y2 = __builtin_nanf("");
   // centre = projection of the reference point (tOR = 0 -> origin of the object frame)
-  float cz = fmaxf(0.1f, P[11]);
+  float cz = max_nan(0.1f, P[11]);
   float xc = P[3] / cz, yc = P[7] / cz;
   // deepim_boxes (TB/lib3d/cropping.py:27-75), obs box == rendered box
-  float xdist = fmaxf(fabsf(x1 - xc), fabsf(x2 - xc));
-  float ydist = fmaxf(fabsf(y1 - yc), fabsf(y2 - yc));
+  float xdist = max_nan(fabsf(x1 - xc), fabsf(x2 - xc));
+  float ydist = max_nan(fabsf(y1 - yc), fabsf(y2 - yc));
   const int wmax = a.im_h > a.im_w ? a.im_h : a.im_w, hmin = a.im_h > a.im_w ? a.im_w : a.im_h;
   const float r = (float)((double)wmax / (double)hmin);
-  float width = fmaxf(xdist, ydist * r) * 2.0f * a.lamb;
-  float height = fmaxf(xdist / r, ydist) * 2.0f * a.lamb;
+  float width = max_nan(xdist, ydist * r) * 2.0f * a.lamb;
+  float height = max_nan(xdist / r, ydist) * 2.0f * a.lamb;
   float bx1 = xc - width / 2.0f, by1 = yc - height / 2.0f, bx2 = xc + width / 2.0f, by2 = yc + height / 2.0f;
   // get_K_crop_resize (TB/lib3d/camera_geometry.py:70-122)
   const float fw = (float)(a.crop_h > a.crop_w ? a.crop_h : a.crop_w);
